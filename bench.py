@@ -2,7 +2,14 @@
 """Headline benchmark: edges/sec of GCN forward+backward on the 10M-edge
 synthetic graph, F = 128 (BASELINE.json `metric`, config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step`, ...).  `--dump-outputs DIR` then writes what the last
+timed step computed (:func:`dump_outputs`).  `--full` adds everything that
+takes runs of its own: the instrumented per-kernel pass (`kernels`,
+`kernel_templates`, `roofline`), the CPU baseline (`cpu_baseline`) and, at
+N > 1 in `--mode auto`, the second parallelisation (`replicas`).
 
 Workload: Erdos-Renyi, N = 1,000,000 nodes,
 5,000,000 random (s, d) pairs drawn with torch.Generator seed 0 (s first,
@@ -20,8 +27,8 @@ N > 1 GPUs (torch.distributed.run, one rank per GPU, RCCL): `value` is the
 edges/s of ONE config-2 graph sharded by destination-node range over the N
 ranks (mgcn.dist: the north star's partitioning, chunked RCCL all-gathers of
 the layer activations and upstream gradients over xGMI overlapped with the
-fused layer kernels; `scaling` "strong").  The same run also times
-data-parallel replicas (every rank its own config-2 graph, one bucketed
+fused layer kernels; `scaling` "strong").  With `--full` the same run also
+times data-parallel replicas (every rank its own config-2 graph, one bucketed
 gradient all-reduce per step) and reports them under `replicas` (`scaling`
 "weak").  `--mode shard|replica` measures one of them as `value`.
 """
@@ -296,7 +303,8 @@ def make_stack(dev, Ws, bs):
 def build_stack(dev, ei_cpu, X, Ws, bs, dY):
     """Single-GPU config-2 model (:func:`make_stack`, the fused libmgcn path)
     on one graph; returns (step, params).  The step is fwd + bwd to every
-    weight and bias against the fixed upstream gradient dY."""
+    weight and bias against the fixed upstream gradient dY, and returns the
+    top layer's output."""
     stack = make_stack(dev, Ws, bs)
     params = list(stack.parameters())
     ei = ei_cpu.to(dev)
@@ -306,13 +314,17 @@ def build_stack(dev, ei_cpu, X, Ws, bs, dY):
     def step():
         for p in params:
             p.grad = None
-        stack(Xd, ei).backward(dYd)
+        y = stack(Xd, ei)
+        y.backward(dYd)
+        return y
     return step, params
 
 
-def timed(run_step, steps, warmup, world, dev, timer=None):
+def timed(run_step, steps, warmup, world, dev, timer=None, after=None):
     """Graph prep + first step (untimed, reported), W warm-up steps, then
     exactly K steps bracketed by barrier + device sync; max over ranks.
+    ``after`` (--dump-outputs) is called once the clock has stopped, with what
+    the last timed step returned, before anything else runs.
     The headline loop runs uninstrumented; with ``timer`` a separate pass of
     min(K, 10) steps afterwards records HIP events around every libmgcn
     launch (per-kernel averages; not part of the headline time)."""
@@ -333,13 +345,19 @@ def timed(run_step, steps, warmup, world, dev, timer=None):
         run_step()
     torch.cuda.synchronize()
     barrier()
+    last = None
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         run_step()
+    if steps > 0:
+        last = run_step()  # the last step's result is kept for --dump-outputs
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     barrier()
     elapsed = t1 - t0
+    if after is not None:
+        after(last)
+    del last
     if timer is not None:  # instrumented pass, outside the timed region
         ops.set_kernel_timer(timer)
         for _ in range(min(steps, 10)):
@@ -355,6 +373,43 @@ def timed(run_step, steps, warmup, world, dev, timer=None):
     return elapsed, prep_ms
 
 
+DUMP_BUDGET = 64 << 20   # bytes, all files of one --dump-outputs together
+DUMP_SEED = 5            # row sample of an output over half the budget
+
+
+def dump_outputs(path: str, y, grads) -> dict:
+    """Write what the last timed step handed its caller as ``path/<name>.npy``
+    (float32): ``y``, the top layer's output [rows, F] (None where the step
+    returns nothing, as the sharded step does), and ``grads``, {name: the
+    gradient the step left on a weight or bias}.  An output over half of
+    DUMP_BUDGET is written as a fixed sample of its rows (ascending row ids
+    of torch.randperm(rows) under torch.Generator seed DUMP_SEED), so two
+    builds run with the same arguments write the same rows.  Returns
+    {name: shape written}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    if y is not None:
+        y = y.detach()
+        row_bytes = 4 * y[0].numel()
+        keep = (DUMP_BUDGET // 2) // row_bytes
+        if y.shape[0] > keep:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            rows = torch.randperm(y.shape[0], generator=g)[:keep].sort().values
+            y = y[rows.to(y.device)]
+        out["y"] = y
+    for name, gr in grads.items():
+        out["grad_" + name] = gr.detach()
+    shapes, total = {}, 0
+    for name, t in out.items():
+        a = np.ascontiguousarray(t.to(torch.float32).cpu().numpy())
+        total += a.nbytes
+        assert total <= DUMP_BUDGET, "dump_outputs: over DUMP_BUDGET"
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -364,8 +419,16 @@ def main():
     ap.add_argument("--pairs", type=int, default=5_000_000)
     ap.add_argument("--feat", type=int, default=128)
     ap.add_argument("--layers", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timers", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the instrumented "
+                         "per-kernel pass (kernels, kernel_templates, roofline), the CPU "
+                         "baseline and, at N > 1 in --mode auto, the replica measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's output (a seeded row "
+                         "sample) and every weight / bias gradient as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-timers", action="store_true",
+                    help="--full without the instrumented per-kernel pass")
     ap.add_argument("--dense-exchange", action="store_true",
                     help="N > 1 sharded: send every exchanged table dense (no zero-skipping)")
     ap.add_argument("--packed-exchange", action="store_true",
@@ -373,8 +436,8 @@ def main():
                          "ranks, mgcn.dist.set_pack_exchange('auto'))")
     ap.add_argument("--mode", choices=["auto", "replica", "shard"], default="auto",
                     help="N > 1: 'auto' measures the dst-range sharded graph (value, strong "
-                         "scaling) and data-parallel replicas (the 'replicas' field, weak "
-                         "scaling); 'shard' / 'replica' measure one of them as value")
+                         "scaling) and, with --full, data-parallel replicas (the 'replicas' "
+                         "field, weak scaling); 'shard' / 'replica' measure one of them as value")
     ap.add_argument("--chunks", type=int, default=4,
                     help="N > 1 sharded path: row chunks per layer output (all-gathers "
                          "pipelined behind the compute)")
@@ -409,13 +472,14 @@ def main():
     F, L = args.feat, args.layers
     n_edges = 2 * args.pairs          # graph edges, self-loops not counted
     X, Ws, bs, dY = make_inputs(args.nodes, F, L)
-    timer = None if args.no_kernel_timers else KernelTimer()
+    timer = KernelTimer() if args.full and not args.no_kernel_timers else None
     mode = args.mode if world > 1 else "replica"
     if mode == "auto":
         mode = "shard"
     do_shard = world > 1 and (args.mode in ("auto", "shard"))
-    do_replica = world == 1 or args.mode in ("auto", "replica")
+    do_replica = world == 1 or args.mode == "replica" or (args.mode == "auto" and args.full)
     sharded = replicas = None
+    dumped = None
     N = args.nodes
     ei_cpu = None
     if do_shard:
@@ -427,8 +491,18 @@ def main():
         model = ShardedGCN(ei_cpu, N, Ws, bs, device=dev, chunks=args.chunks)
         nnz = ei_cpu.shape[1]
         mdist.STATS.update(dense_words=0, sent_words=0)
+
+        def dump_sharded(_):
+            # the sharded step returns nothing: its caller receives the
+            # all-reduced gradients
+            nonlocal dumped
+            grads = {f"W{i}": w.grad for i, w in enumerate(model.W)}
+            grads.update({f"b{i}": b.grad for i, b in enumerate(model.b)})
+            dumped = dump_outputs(args.dump_outputs, None, grads)
+        dump = args.dump_outputs and mode == "shard" and rank == 0
         t_sh, prep_sh = timed(model.step_fn(X, dY), args.steps, args.warmup, world, dev,
-                              timer if mode == "shard" else None)
+                              timer if mode == "shard" else None,
+                              dump_sharded if dump else None)
         st = dict(mdist.STATS)
         sharded = {"value": n_edges * L / (t_sh / args.steps), "unit": "edges/s",
                    "ms_per_step": t_sh / args.steps * 1e3, "scaling": "strong",
@@ -455,10 +529,19 @@ def main():
         step, params = build_stack(dev, ei_r, X, Ws, bs, dY)
 
         def run_step():
-            step()
+            y = step()
             allreduce_grads(params)
+            return y
+
+        def dump_stack(y):
+            # make_stack's parameters: W0, b0, W1, b1, ...
+            nonlocal dumped
+            grads = {f"{'Wb'[i % 2]}{i // 2}": p.grad for i, p in enumerate(params)}
+            dumped = dump_outputs(args.dump_outputs, y, grads)
+        dump = args.dump_outputs and mode == "replica" and rank == 0
         t_r, prep_r = timed(run_step, args.steps, args.warmup, world, dev,
-                            timer if mode == "replica" else None)
+                            timer if mode == "replica" else None,
+                            dump_stack if dump else None)
         replicas = {"value": world * n_edges * L / (t_r / args.steps), "unit": "edges/s",
                     "ms_per_step": t_r / args.steps * 1e3, "scaling": "weak",
                     "parallelism": f"dp{world}" if world > 1 else "single",
@@ -490,6 +573,8 @@ def main():
                    "parallelism": head["parallelism"]},
         "graph_prep_plus_first_step_ms": head["graph_prep_plus_first_step_ms"],
     }
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
     if world > 1:
         if mode == "shard" and replicas is not None:
             result["replicas"] = replicas
@@ -545,7 +630,7 @@ def main():
                                       "(bench.launch_bytes, launch-weighted over its forms) / its "
                                       "average HIP-event launch time; the dominant template by "
                                       "GPU time, as rocprofv3 --stats reports kernels"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(ei_cpu, X, Ws[1], bs[1], n_edges)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -19,7 +19,7 @@ if [ -n "$TESTS" ]; then
   tail -1 "$O/tests.log"
 fi
 case $W in
-  bench) cmd="python -u bench.py --no-cpu-baseline" ;;
+  bench) cmd="python -u bench.py --full --no-cpu-baseline" ;;
   config3) cmd="python -u scripts/bench_workloads.py --workload config3" ;;
   config4) cmd="python -u scripts/bench_workloads.py --workload config4 --timers" ;;
   config4max) cmd="python -u scripts/bench_workloads.py --workload config4 --aggr max --timers" ;;

@@ -18,7 +18,7 @@ else
 fi
 tail -1 $O/gpu_tests.log
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-timeout -k 10 300 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python3 -c "
 import json;d=json.load(open('$O/bench_default.json'));print('bench', round(d['ms_per_step'],4), {k:round(v['avg_ms'],4) for k,v in d['kernels'].items()})"
 timeout -k 10 200 python -u scripts/bench_workloads.py --workload config3 > $O/config3.json
@@ -26,7 +26,7 @@ timeout -k 10 300 python -u scripts/bench_workloads.py --workload config4 > $O/c
 cat $O/config3.json $O/config4.json
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- \
-  python3 $R/bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+  python3 $R/bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -o c3 -- \
   python3 $R/scripts/bench_workloads.py --workload config3 > /dev/null 2>&1
 echo gpu_check $T done

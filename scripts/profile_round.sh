@@ -13,10 +13,10 @@ R=$PWD
 T=${1:?tag}
 O=$R/gpurun_out/$T
 mkdir -p $O
-timeout -k 10 300 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- \
-  python3 $R/bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+  python3 $R/bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 for k in fwd fwd_z bwd bwd_dw bwd_dx gemm_dw gemm_dw_cs; do
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 90 rocprofv3 --pmc $c --output-format csv -d $O/pmc_${k}_$c -o pmc -- \

@@ -178,11 +178,9 @@ def test_sharded_fused_matches_single_gpu_stack(cuda):
         torch.testing.assert_close(g, p.grad, rtol=1e-5, atol=1e-5 * float(p.grad.abs().max()))
 
 
-def test_bench_two_ranks_end_to_end(cuda):
-    """bench.py's N > 1 path as the driver launches it (torch.distributed.run,
-    one process per rank), at a reduced size, with gloo and both ranks on
-    cuda:0: the dst-range sharded measurement (`value`, strong) and the
-    replica one (`replicas`, weak) both run and rank 0 prints one JSON line."""
+def _bench_two_ranks(*extra):
+    """bench.py --gpus 2 under torch.distributed.run at a reduced size, gloo,
+    both ranks on cuda:0; returns rank 0's JSON line."""
     import json
     import subprocess
     root = os.path.dirname(HERE)
@@ -191,13 +189,45 @@ def test_bench_two_ranks_end_to_end(cuda):
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--nodes", "20000", "--pairs", "100000", "--dist-backend", "gloo", "--one-device",
-           "--no-cpu-baseline"]
+           *extra]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
-    r = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_bench_two_ranks_end_to_end(cuda):
+    """bench.py's N > 1 path as the driver launches it (torch.distributed.run,
+    one process per rank), at a reduced size, with gloo and both ranks on
+    cuda:0: with --full the dst-range sharded measurement (`value`, strong)
+    and the replica one (`replicas`, weak) both run and rank 0 prints one
+    JSON line."""
+    r = _bench_two_ranks("--full", "--no-cpu-baseline")
     assert r["n_gpus"] == 2 and r["scaling"] == "strong" and r["value"] > 0
     assert r["config"]["parallelism"] == "dst-range x2" and r["config"]["global_batch"] == 1
     assert r["replicas"]["scaling"] == "weak" and r["replicas"]["value"] > 0
     assert r["roofline"]["frac"] > 0 and r["roofline"]["kernel"].startswith("spmm_xw")
+
+
+def test_bench_two_ranks_plain_run_dumps_gradients(cuda, tmp_path):
+    """The same launch without --full: the sharded measurement alone, and
+    --dump-outputs writes what the sharded step leaves its caller, the
+    all-reduced weight and bias gradients -- the single-device stack's
+    (bench.build_stack on the same inputs) within fp32 summation order."""
+    import bench
+    d = str(tmp_path / "dump")
+    r = _bench_two_ranks("--dump-outputs", d)
+    assert r["n_gpus"] == 2 and r["scaling"] == "strong" and r["value"] > 0 and r["ms_per_step"] > 0
+    assert not any(k in r for k in ("replicas", "roofline", "kernels", "cpu_baseline"))
+    names = [f"grad_{p}{i}" for i in range(3) for p in "Wb"]
+    assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in names)
+    ei, N = bench.make_er_graph(20000, 100000)
+    X, Ws, bs, dY = bench.make_inputs(N, 128, 3)
+    step, params = bench.build_stack(cuda, ei, X, Ws, bs, dY)
+    step()
+    for i, p in enumerate(params):  # W0, b0, W1, b1, ...
+        got = np.load(os.path.join(d, f"grad_{'Wb'[i % 2]}{i // 2}.npy"))
+        g = p.grad.cpu().numpy()
+        assert got.dtype == np.float32
+        np.testing.assert_allclose(got, g, rtol=1e-5, atol=1e-5 * float(np.abs(g).max()))
