@@ -804,6 +804,99 @@ int mgcn_spmm_xw_bwd_packed(int64_t n_rows, int32_t F_in, int32_t F_out, const i
                             float *colsum, int accumulate, void *workspace,
                             size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------- attention node model */
+
+/*
+ * Multi-head soft attention over a node's neighbourhood: the message passing
+ * of NodeModelAttention (src/gcn_meta/models/graph_attention.py:60-117) with
+ * the sparse softmax of src/gcn_meta/models/common.py:69-92, and its adjoint.
+ * These entry points were added under ABI 22 without changing any existing
+ * one (a backward-compatible addition: MGCN_ABI_VERSION stays 22).
+ *
+ * Hp = X W is [N, H C] (head h in columns [h C, h C + C), row stride ldh) and
+ * a is the attention vector [H, 2C], contiguous (att_weight [1, H, 2C]).  For
+ * edge k (j -> i):  z_k[h] = s_src[j,h] + s_dst[i,h],  e = act(z),
+ *   alpha_k = exp(e_k - m) / (sum_group exp(e - m) + 1e-16),
+ *   m = max(-1e16, max_group e),
+ * the group being the row of the CSR view the call walks.  Per-edge arrays
+ * (alpha, mask, dz) are [nnz, H] contiguous.  Supported: 1 <= H <= 16, C >= 1,
+ * H C <= 1024, nnz H < 2^31, any leading dimension >= H C; anything else
+ * returns MGCN_EINVAL before a launch.  n_rows == 0 is a successful no-op.
+ * No atomics; rows keep COO order and every sum has a fixed order, so results
+ * are bitwise repeatable (equal to the reference to fp32 rounding: its CPU
+ * summation order differs).
+ */
+#define MGCN_ATT_ACT_NONE 0
+#define MGCN_ATT_ACT_LRELU 1 /* LeakyReLU(0.2), common.py:27 */
+#define MGCN_ATT_ACT_RELU 2
+
+/* s_src[n,h] = sum_c Hp[n,h,c] a[h,c],  s_dst[n,h] = sum_c Hp[n,h,c] a[h,C+c]
+ * ([n, H] contiguous); products summed per lane in column order, then a
+ * fixed butterfly. */
+int mgcn_att_scores(int64_t n, int32_t H, int32_t C, const float *Hp, int64_t ldh,
+                    const float *a, float *s_src, float *s_dst, void *stream);
+
+/*
+ * The forward over a view whose rows are destinations (rowptr / col of the
+ * fwd view; col = sources), in one launch:
+ *   alpha_in == NULL:  z = s_row[row] + s_col[col]  (s_row = s_dst, s_col =
+ *     s_src), the softmax over the row, alpha written in slot order;
+ *   alpha_in != NULL:  alpha = alpha_in (att_dir = 'out': softmax taken over
+ *     the source-grouped view by mgcn_edge_softmax and carried to fwd slot
+ *     order); s_row / s_col / alpha are not used.
+ *   Y[row,h,:] = sum_k alpha_k[h] mask_k[h] Hp[col_k,h,:]   (mask NULL: ones),
+ * summed in slot (COO) order.  The stored alpha is the one before the mask.
+ */
+int mgcn_att_fwd(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr,
+                 const int32_t *col, const float *s_row, const float *s_col, int act,
+                 const float *alpha_in, const float *mask, const float *Hp, int64_t ldh,
+                 float *Y, int64_t ldy, float *alpha, void *stream);
+
+/* The same logits and softmax over any view (groups = rows), no gather:
+ * alpha in the view's slot order (the same device code as mgcn_att_fwd). */
+int mgcn_edge_softmax(int64_t n_rows, int64_t nnz, int32_t H, const int64_t *rowptr,
+                      const int32_t *col, const float *s_row, const float *s_col, int act,
+                      float *alpha, void *stream);
+
+/*
+ * Adjoint by destination row (fwd view), from dY [N, H C]:
+ *   dalpha_k[h] = mask_k[h] sum_c dY[row,h,c] Hp[col_k,h,c]   (per-head SDDMM)
+ *   softmax == 0: dz := dalpha                                 (att_dir 'out')
+ *   softmax != 0: dz_k = alpha_k (dalpha_k - sum_row alpha dalpha) act'(z_k),
+ *                 ds_row[row,h] = sum_k dz_k[h]  (= ds_dst)    (att_dir 'in')
+ * dz in fwd slot order.
+ */
+int mgcn_att_bwd_dst(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr,
+                     const int32_t *col, const float *Hp, int64_t ldh, const float *dY,
+                     int64_t lddy, const float *alpha, const float *mask, const float *s_row,
+                     const float *s_col, int act, int softmax, float *dz, float *ds_row,
+                     void *stream);
+
+/*
+ * Adjoint by source row (the bwd view rowptr_t / col_t, col_t = destinations;
+ * slot_map = mgcn_slot_map: the fwd slot of every bwd slot; alpha, mask and dz
+ * are in fwd slot order):
+ *   softmax != 0 (att_dir 'out'): dz (holding dalpha) is replaced in place by
+ *     alpha (dalpha - sum_row alpha dalpha) act'(z), z = s_row[row] + s_col[col]
+ *     (s_row = s_src, s_col = s_dst);
+ *   ds_src[row,h] = sum_k dz_k[h]
+ *   dHp[row,h,:] = sum_k alpha_k mask_k dY[col_k,h,:] + ds_src[row,h] a[h,:C]
+ *                  (+ ds_dst[row,h] a[h,C:] when ds_dst != NULL: 'in', where
+ *                  mgcn_att_bwd_dst has produced it; 'out': mgcn_att_dst_fold)
+ */
+int mgcn_att_bwd_src(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr_t,
+                     const int32_t *col_t, const int32_t *slot_map, const float *dY,
+                     int64_t lddy, const float *alpha, const float *mask, float *dz,
+                     const float *s_row, const float *s_col, int act, int softmax,
+                     const float *a, const float *ds_dst, float *ds_src, float *dHp,
+                     int64_t lddh, void *stream);
+
+/* att_dir 'out', after mgcn_att_bwd_src: over the fwd view,
+ * ds_dst[row,h] = sum_k dz_k[h]  and  dHp[row,h,:] += ds_dst[row,h] a[h,C:]. */
+int mgcn_att_dst_fold(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr,
+                      const float *dz, const float *a, float *ds_dst, float *dHp, int64_t lddh,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ OK, EINVAL, EINDEX, EHIP, EWORKSPACE, EDEVICE = 0, 1, 2, 3, 4, 5
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
 NORM_NONE, NORM_SM, NORM_RW = 0, 1, 2
 MAX_FILL = -1e38
+ATT_ACT_CODES = {"none": 0, "lrelu": 1, "relu": 2}
 
 REDUCE_CODES = {"add": REDUCE_SUM, "sum": REDUCE_SUM, "mean": REDUCE_MEAN, "max": REDUCE_MAX}
 NORM_CODES = {None: NORM_NONE, "sm": NORM_SM, "rw": NORM_RW}
@@ -124,6 +125,15 @@ SIGNATURES = {
     "mgcn_residual_layer_bwd": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
                                        _int, _int, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
                                        _vp, _i64, _i64, _vp, _sz, _vp]),
+    "mgcn_att_scores": (_int, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "mgcn_att_fwd": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _i64,
+                            _vp, _i64, _vp, _vp]),
+    "mgcn_edge_softmax": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
+    "mgcn_att_bwd_dst": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
+                                _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "mgcn_att_bwd_src": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mgcn_att_dst_fold": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 class PackedTableC(ctypes.Structure):

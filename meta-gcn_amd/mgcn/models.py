@@ -6,6 +6,7 @@ direction and the training scripts (src/run/train_botnet.py:190-294) run
 unchanged after swapping the import:
 
   NodeModelBase / NodeModelAdditive  gcn_base_models.py:11-243
+  NodeModelAttention                 graph_attention.py:11-123
   GCNMultiKernel                     gcn_multi_kernel.py:9-114
   GCNLayer / GCNModel                gcn_model.py:8-197
   activation / Identity / scatter_   common.py:11-66
@@ -28,7 +29,7 @@ from torch.nn.utils.rnn import pad_sequence
 
 from . import _lib as L
 from .graph import plan_for
-from .ops import (aggregate_plan, gcn_layer, gcn_stack, linear, linear_bias,  # noqa: F401
+from .ops import (aggregate_plan, attention_aggregate, gcn_layer, gcn_stack, linear, linear_bias,  # noqa: F401
                   residual_gcn_layer, residual_layer_supported, residual_stack,  # noqa: F401
                   scatter_)
 
@@ -192,19 +193,94 @@ class NodeModelAdditive(NodeModelBase):
         return aggregate_plan(x, plan, norm, self.aggr, self.bias, relu)
 
 
+# ------------------------------------------------------ graph_attention.py
+class NodeModelAttention(NodeModelBase):
+    """graph_attention.py:11-123: multi-head soft attention over a node's
+    neighbourhood.  ``x @ W`` runs on :func:`mgcn.ops.linear`; scores, the
+    per-neighbourhood softmax, the dropout mask and the per-head weighted
+    gather are :func:`mgcn.ops.attention_aggregate`.  As in the reference,
+    deg_norm / edge_gate / aggr keep NodeModelBase's defaults and are unused,
+    and with ``att_combine='cat'`` one head has out_channels / nheads channels
+    (else out_channels each)."""
+
+    def __init__(self, in_channels, out_channels, in_edgedim=None, nheads=1, att_act='none',
+                 att_dropout=0, att_combine='cat', att_dir='in', bias=False, **kwargs):
+        assert att_act in ['none', 'lrelu', 'relu']
+        assert att_combine in ['cat', 'add', 'mean']
+        assert att_dir in ['in', 'out']
+        super().__init__(in_channels, out_channels, in_edgedim)
+        self.nheads = nheads
+        if att_combine == 'cat':
+            self.out_channels_1head = out_channels // nheads
+            assert self.out_channels_1head * nheads == out_channels, \
+                'out_channels should be divisible by nheads'
+        else:
+            self.out_channels_1head = out_channels
+        self.att_combine = att_combine
+        self.att_dir = att_dir
+        self.att_act_name = att_act
+        self.weight = Parameter(torch.Tensor(in_channels, self.out_channels_1head * nheads))
+        self.att_weight = Parameter(torch.Tensor(1, nheads, 2 * self.out_channels_1head))
+        self.att_act = activation(att_act)
+        self.att_dropout = nn.Dropout(p=att_dropout)
+        if bias:
+            self.bias = Parameter(torch.Tensor(out_channels))
+        else:
+            self.register_parameter('bias', None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot(self.weight)
+        glorot(self.att_weight)
+        zeros(self.bias)
+
+    def forward(self, x, edge_index, edge_attr=None, deg=None, edge_weight=None, attn_store=None,
+                **kwargs):
+        """'deg' and 'edge_weight' are not used (as in the reference).
+        ``attn_store`` (a list) receives this call's attention coefficients
+        after dropout, [E, nheads] in COO edge order, detached."""
+        plan = plan_for(edge_index, x.size(0))
+        hp = linear(x, self.weight)
+        mask = None
+        if self.training and self.att_dropout.p > 0:
+            # the reference's Dropout on alpha: alpha * mask with mask = dropout(ones)
+            mask = nn.functional.dropout(
+                torch.ones(plan.nnz, self.nheads, dtype=torch.float32, device=hp.device),
+                p=self.att_dropout.p, training=True)
+        y, alpha = attention_aggregate(hp, self.att_weight, plan, self.nheads,
+                                       self.att_act_name, self.att_dir, edge_mask=mask)
+        if self.att_combine == 'add':
+            y = y.view(-1, self.nheads, self.out_channels_1head).sum(dim=1)
+        elif self.att_combine == 'mean':
+            y = y.view(-1, self.nheads, self.out_channels_1head).mean(dim=1)
+        if self.bias is not None:
+            y = y + self.bias
+        if attn_store is not None:
+            attn_store.append(alpha)
+        return y
+
+    def __repr__(self):
+        return ('{} (in_channels: {}, out_channels: {}, in_edgedim: {}, nheads: {}, '
+                'att_activation: {},att_dropout: {}, att_combine: {}, att_dir: {} | '
+                'number of parameters: {}').format(
+                    self.__class__.__name__, self.in_channels, self.out_channels,
+                    self.in_edgedim, self.nheads, self.att_act, self.att_dropout.p,
+                    self.att_combine, self.att_dir, self.num_parameters())
+
+
 # ------------------------------------------------------ gcn_multi_kernel.py
 class GCNMultiKernel(nn.Module):
-    """gcn_multi_kernel.py:9-114.  Only the 'additive' node model runs on this
-    engine; attention / hard-attention node models are out of scope."""
+    """gcn_multi_kernel.py:9-114.  The 'additive' and 'attention' node models
+    run on this engine; the sampling-based hard attention is out of scope."""
 
-    nodemodel_dict = {'additive': NodeModelAdditive}
+    nodemodel_dict = {'additive': NodeModelAdditive, 'attention': NodeModelAttention}
 
     def __init__(self, *args, num_kernel=1, nodemodel='additive', kernel_combine='add',
                  **kwargs):
         assert nodemodel in ['additive', 'attention', 'hardattention']
         assert kernel_combine in ['add', 'cat', 'mean']
         super().__init__()
-        if nodemodel != 'additive':
+        if nodemodel not in self.nodemodel_dict:
             raise NotImplementedError(f"nodemodel={nodemodel!r} is not supported by mgcn")
         self.kernel_combine = kernel_combine
         self.node_models = nn.ModuleList(
@@ -231,16 +307,18 @@ class GCNMultiKernel(nn.Module):
 
     def forward(self, x, edge_index_K, edge_attr_K=None, deg_K=None, edge_weight_K=None,
                 **kwargs):
-        return self.forward_fused(x, edge_index_K, edge_attr_K, deg_K, edge_weight_K, relu=False)
+        return self.forward_fused(x, edge_index_K, edge_attr_K, deg_K, edge_weight_K, relu=False,
+                                  **kwargs)
 
     def can_fuse_relu(self, edge_index_K) -> bool:
         if isinstance(edge_index_K, torch.Tensor):
             edge_index_K = [edge_index_K]
         return len(self.node_models) == 1 and len(edge_index_K) == 1 \
-            and edge_index_K[0] is not None
+            and edge_index_K[0] is not None \
+            and all(isinstance(nm, NodeModelAdditive) for nm in self.node_models)
 
     def forward_fused(self, x, edge_index_K, edge_attr_K=None, deg_K=None, edge_weight_K=None,
-                      relu=False):
+                      relu=False, **kwargs):
         eis, eas, degs, ews = self._listify(edge_index_K, edge_attr_K, deg_K, edge_weight_K)
         if relu:
             assert self.can_fuse_relu(edge_index_K)
@@ -252,7 +330,10 @@ class GCNMultiKernel(nn.Module):
                                                                ews):
             if edge_index is None:
                 continue
-            y = nm(x, edge_index, edge_attr, deg, edge_weight)
+            if isinstance(nm, NodeModelAttention):
+                y = nm(x, edge_index, edge_attr, deg, edge_weight, **kwargs)  # attn_store
+            else:
+                y = nm(x, edge_index, edge_attr, deg, edge_weight)
             outs.append(y)
         if not outs:
             return 0
@@ -277,7 +358,8 @@ class GCNLayer(nn.Module):
                  aggr='add', bias=True, num_kernel=1, nodemodel='additive', non_linear='relu',
                  **kwargs):
         super().__init__()
-        kwargs.pop('nheads', None)  # attention-only argument (gcn_model.py:49)
+        if nodemodel != 'attention':
+            kwargs.pop('nheads', None)  # attention-only argument (gcn_model.py:49)
         self.gcn = GCNMultiKernel(in_channels, out_channels, in_edgedim, deg_norm=deg_norm,
                                   edge_gate=edge_gate, aggr=aggr, bias=bias,
                                   num_kernel=num_kernel, nodemodel=nodemodel, **kwargs)
@@ -314,6 +396,8 @@ class GCNStack(nn.Module):
             g = layer.gcn
             if len(g.node_models) != 1 or layer.non_linear_name not in ('relu', 'none'):
                 return None
+            if not isinstance(g.node_models[0], NodeModelAdditive):
+                return None  # attention layers: layer by layer
             nms.append(g.node_models[0])
         if len({(nm.deg_norm, nm.aggr) for nm in nms}) != 1:
             return None
@@ -417,6 +501,8 @@ class GCNModel(nn.Module):
         for layer in self.gcn_net:
             if len(layer.gcn.node_models) != 1 or layer.non_linear_name not in ('relu', 'none'):
                 return False
+            if not isinstance(layer.gcn.node_models[0], NodeModelAdditive):
+                return False  # attention layers: step for step
         return True
 
     def forward(self, x, edge_index_K, edge_attr_K=None, deg_K=None, edge_weight_K=None,
@@ -494,5 +580,5 @@ class GCNModel(nn.Module):
 
 
 __all__ = ["glorot", "zeros", "Identity", "activation", "scatter_", "Linear", "NodeModelBase",
-           "NodeModelAdditive", "GCNMultiKernel", "GCNLayer", "GCNStack", "GCNModel"]
+           "NodeModelAdditive", "NodeModelAttention", "GCNMultiKernel", "GCNLayer", "GCNStack", "GCNModel"]
 _ = L  # keep the binding imported so a missing library fails at import of ops

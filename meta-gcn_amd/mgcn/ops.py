@@ -1781,6 +1781,156 @@ def residual_gcn_layer(x, plan: GraphPlan, norm: NormPlan, aggr: str, relu1: boo
     return _ResidualGCNLayer.apply(x, plan, norm, reduce, bool(relu1), bool(relu2), W, b, Wr, br)
 
 
+# --------------------------------------------------------------- attention
+def _att_call(name: str, view: CSRView | None, rows: int, fn) -> None:
+    """One libmgcn attention launch, bracketed by the kernel timer."""
+    if _TIMER is not None:
+        _TIMER(name, True, rows, view.edges if view is not None else None)
+    rc = fn()
+    if _TIMER is not None:
+        _TIMER(name, False)
+    L.check(rc, "mgcn_" + name)
+
+
+class _AttentionAggregate(torch.autograd.Function):
+    """The message passing of NodeModelAttention after its ``x @ W``
+    (graph_attention.py:66-100) on libmgcn's attention kernels.
+
+    Forward: mgcn_att_scores, then for 'in' one mgcn_att_fwd launch (logits,
+    softmax by destination, weighted gather); for 'out' mgcn_edge_softmax over
+    the source-grouped view, alpha carried to fwd slot order, mgcn_att_fwd in
+    its aggregate-only mode.  Saved: Hp, alpha (fwd slot order, before the
+    dropout mask), the slot-order mask, s_src / s_dst.  Backward:
+    mgcn_att_bwd_dst, mgcn_att_bwd_src (+ mgcn_att_dst_fold for 'out'), and the
+    attention vector's gradient as one mgcn_gemm_tn ([ds_src | ds_dst]^T Hp,
+    of which head h's own C columns are its rows of da)."""
+
+    @staticmethod
+    def forward(ctx, Hp, att, mask, plan: GraphPlan, H: int, act: int, att_dir: str):
+        lib = L.load()
+        dev = Hp.device
+        N, HC = Hp.shape
+        C = HC // H
+        nnz = plan.nnz
+        st = L.stream_of(dev)
+        att = att.detach().contiguous()
+        s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+        s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
+        Y = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+        fwd, bwd = plan.fwd, plan.bwd
+        with L.device_guard(dev):
+            _att_call("att_scores", None, N, lambda: lib.mgcn_att_scores(
+                N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st))
+            if att_dir == 'in' or nnz == 0:
+                _att_call("att_fwd", fwd, N, lambda: lib.mgcn_att_fwd(
+                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst), L.ptr(s_src),
+                    act, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, L.ptr(alpha),
+                    st))
+            else:
+                a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+                _att_call("edge_softmax", bwd, N, lambda: lib.mgcn_edge_softmax(
+                    N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
+                    L.ptr(a_bwd), st))
+                alpha[plan.slot_map()[:nnz].long()] = a_bwd
+                _att_call("att_fwd", fwd, N, lambda: lib.mgcn_att_fwd(
+                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act,
+                    L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None, st))
+        ctx.plan, ctx.H, ctx.act, ctx.att_dir = plan, H, act, att_dir
+        ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
+        ctx.mark_non_differentiable(alpha)
+        return Y, alpha
+
+    @staticmethod
+    def backward(ctx, dY, _dalpha):
+        Hp, att, alpha, mask, s_src, s_dst = ctx.saved_tensors
+        plan, H, act = ctx.plan, ctx.H, ctx.act
+        lib = L.load()
+        dev = Hp.device
+        N, HC = Hp.shape
+        C = HC // H
+        nnz = plan.nnz
+        st = L.stream_of(dev)
+        dY = _contig_f32(dY, "dY")
+        fwd, bwd = plan.fwd, plan.bwd
+        slot = plan.slot_map() if nnz else None
+        dz = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+        ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+        ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
+        dHp = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        inn = ctx.att_dir == 'in'
+        with L.device_guard(dev):
+            _att_call("att_bwd_dst", fwd, N, lambda: lib.mgcn_att_bwd_dst(
+                N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
+                L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst), L.ptr(s_src),
+                act, int(inn), L.ptr(dz), L.ptr(ds_dst), st))
+            _att_call("att_bwd_src", bwd, N, lambda: lib.mgcn_att_bwd_src(
+                N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
+                dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
+                act, int(not inn), L.ptr(att), L.ptr(ds_dst) if inn else None, L.ptr(ds_src),
+                L.ptr(dHp), HC, st))
+            if not inn:
+                _att_call("att_dst_fold", fwd, N, lambda: lib.mgcn_att_dst_fold(
+                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(dz), L.ptr(att), L.ptr(ds_dst),
+                    L.ptr(dHp), HC, st))
+        datt = None
+        if ctx.needs_input_grad[1]:
+            full = gemm_tn(torch.cat([ds_src, ds_dst], dim=1), Hp)
+            full = full.view(2, H, H, C)  # [src | dst, head of ds, head of Hp, c]
+            hh = torch.arange(H, device=dev)
+            datt = torch.cat([full[0, hh, hh], full[1, hh, hh]], dim=1)  # [H, 2C]
+        return dHp, datt, None, None, None, None, None
+
+
+def attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphPlan, nheads: int,
+                        act: str = 'none', att_dir: str = 'in',
+                        edge_mask: torch.Tensor | None = None):
+    """Multi-head soft attention over each node's neighbourhood
+    (graph_attention.py:66-100 + the softmax of common.py:69-92), fused:
+
+    ``Hp`` [N, H * C] (or [N, H, C]) are the transformed features, ``att_weight``
+    [1, H, 2C] (or [H, 2C]) the attention vector, ``act`` in none / lrelu /
+    relu, ``att_dir`` 'in' (softmax over the edges into a node) or 'out' (over
+    the edges out of it).  ``edge_mask`` [E, H], in COO edge order, multiplies
+    the attention coefficients (the dropout mask with its 1 / (1 - p) scale).
+
+    Returns ``(Y, alpha_coo)``: Y [N, H * C] = sum over in-edges of alpha' *
+    Hp[src], and alpha' = alpha * mask as [E, H] in COO order, detached.
+    Differentiable in Hp and att_weight.  CPU tensors raise: no CPU path."""
+    L.require_device(Hp, att_weight, plan.fwd.rowptr, edge_mask)
+    if act not in L.ATT_ACT_CODES:
+        raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
+    if att_dir not in ('in', 'out'):
+        raise ValueError(f"att_dir must be 'in' or 'out', got {att_dir!r}")
+    H = int(nheads)
+    Hp2 = _contig_f32(Hp.reshape(Hp.size(0), -1), "Hp")
+    if Hp2.size(0) != plan.num_nodes:
+        raise ValueError(f"Hp has {Hp2.size(0)} rows, graph has {plan.num_nodes} nodes")
+    HC = Hp2.size(1)
+    if H < 1 or HC % H:
+        raise ValueError(f"Hp width {HC} is not a multiple of nheads = {H}")
+    C = HC // H
+    if att_weight.dtype != torch.float32 or att_weight.numel() != 2 * HC:
+        raise ValueError(f"att_weight must be float32 [1, {H}, {2 * C}], got "
+                         f"{att_weight.dtype} {tuple(att_weight.shape)}")
+    if not (1 <= H <= 16 and HC <= 1024 and plan.nnz * H < 2 ** 31):
+        raise L.MgcnError(f"attention_aggregate: unsupported shape (H = {H}, C = {C}, nnz = "
+                          f"{plan.nnz}): need 1 <= H <= 16, H C <= 1024, nnz H < 2^31")
+    mask = None
+    if edge_mask is not None:
+        if tuple(edge_mask.shape) != (plan.nnz, H):
+            raise ValueError(f"edge_mask must be [{plan.nnz}, {H}] in COO order, got "
+                             f"{tuple(edge_mask.shape)}")
+        mask = edge_mask.detach().to(torch.float32)[plan.fwd.eid.long()].contiguous()
+    Y, alpha = _AttentionAggregate.apply(Hp2, att_weight.reshape(H, 2 * C), mask, plan, H,
+                                         L.ATT_ACT_CODES[act], att_dir)
+    alpha = alpha.detach()
+    alpha_coo = torch.empty_like(alpha)
+    if plan.nnz:
+        alpha_coo[plan.fwd.eid.long()] = alpha * mask if mask is not None else alpha
+    return Y, alpha_coo
+
+
 # ---------------------------------------------------------------- scatter_
 class _SegmentReduce(torch.autograd.Function):
     """torch_scatter 1.x scatter_{add,mean,max}(src, index, 0, None, dim_size)
