@@ -113,6 +113,11 @@ int mgcn_check_device(void *stream, int sync);
  *   "spmm_xw_unroll": gathers in flight per row of the fused 128-wide layer
  *                   forward, 4 / 5 (default) / 6 / 8 (the two-phase adjoints:
  *                   8, else 4); every value folds in edge order (same bits)
+ *   "xw_dyn_rounds": the last rounds of the 128-wide forward's chunks whose
+ *                   workgroup is decided on the device (claimed from a
+ *                   counter in the call's workspace, so that the workgroups
+ *                   end together), 0 .. 64, default 8; 0 = every chunk goes
+ *                   to workgroup c mod grid.  Per-row results: same bits.
  *   "xw_ws_full"  : 1 (default) = mgcn_spmm_xw_bwd's dW (+ dX) form on the
  *                   warp-specialised kernel (DWS), 0 = the two-phase kernel
  *   "xw_ws_max"   : 1 (default) = the max adjoint with dX on DWS as well
@@ -398,7 +403,10 @@ int mgcn_spmm_xw_supported(int32_t F_in, int32_t F_out, int reduce);
 /* 1 if mgcn_spmm_xw_bwd's dW-accumulating form and its max adjoint apply
  * (128 x 128 only). */
 int mgcn_spmm_xw_bwd_full_supported(int32_t F_in, int32_t F_out);
-/* Bytes of scratch mgcn_spmm_xw_fwd needs: 0 at 128, the split W image at 256. */
+/* Bytes of scratch mgcn_spmm_xw_fwd takes: at 128 the chunk counter and the
+ * workgroups' mailbox words of the dynamic claim ("xw_dyn_rounds"; optional
+ * there: without it every chunk is assigned statically), the split W image
+ * at 256. */
 size_t mgcn_spmm_xw_fwd_workspace_bytes(int32_t F_in, int32_t F_out);
 
 /*
@@ -422,7 +430,8 @@ size_t mgcn_spmm_xw_fwd_workspace_bytes(int32_t F_in, int32_t F_out);
  * MEAN) with mgcn_gemm_bwd instead of a second gather over the graph
  * (the adjoint of `x @ weight_node`, gcn_base_models.py:201, reassociated).
  * At F = 256 (fused_wide.hip) W is split once per call into a fragment
- * image in `workspace` (mgcn_spmm_xw_fwd_workspace_bytes; NULL at 128), Y
+ * image in `workspace` (mgcn_spmm_xw_fwd_workspace_bytes; at 128 the
+ * workspace may be NULL: it only holds the dynamic claim's counter), Y
  * needs 16-byte aligned rows, and relu_mask holds 8 words per row (feature f
  * at word 4 (f >> 7) + (f & 3), bit (f & 127) >> 2).
  */

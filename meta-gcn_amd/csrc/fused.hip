@@ -504,6 +504,26 @@ __device__ __forceinline__ int64_t my_chunks(int64_t n_chunks) {
   return blockIdx.x < n_chunks ? (n_chunks - 1 - blockIdx.x) / gridDim.x + 1 : 0;
 }
 
+#if MGCN_EXPERIMENT
+// Experiment builds: when every workgroup of the forward (0) and of the
+// warp-specialised adjoint (1) starts and ends (scripts/prof_tail.py: the
+// tail a kernel spends waiting for its last workgroups) -- [kernel][workgroup]
+// {entry, exit (the latest wave's), chunks}, wall_clock64() ticks; read and
+// cleared by mgcn_debug_xw_tail
+constexpr int kTailMaxWg = 1024;
+__device__ unsigned long long g_tail[2][kTailMaxWg][4];
+#define XTAIL_ENTRY(k)                                           \
+  if (threadIdx.x == 0 && blockIdx.x < kTailMaxWg) g_tail[k][blockIdx.x][0] = wall_clock64();
+#define XTAIL_EXIT(k, chunks)                                                         \
+  if ((threadIdx.x & 63) == 0 && blockIdx.x < kTailMaxWg) {                           \
+    atomicMax(&g_tail[k][blockIdx.x][1], (unsigned long long)wall_clock64());         \
+    if (threadIdx.x == 0) g_tail[k][blockIdx.x][2] = (unsigned long long)(chunks);    \
+  }
+#else
+#define XTAIL_ENTRY(k)
+#define XTAIL_EXIT(k, chunks)
+#endif
+
 // One row's four features -> its three bf16 term images (lane gl of the group)
 __device__ __forceinline__ void store_row_terms(char *img_base, int lr, int gl, const float (&v)[4]) {
   uint32_t hi[2], mid[2], lo[2];
@@ -557,14 +577,34 @@ struct XwArgs {
   int64_t ldz;
   int mean;
   int relu;
+  // DYN kernel (launch_xw_dyn): the chunks from dyn_first on are claimed from
+  // claim[0] (zeroed before the launch); mail: [grid][2] words
+  int32_t dyn_first;
+  uint32_t *claim;
+  int32_t *mail;
   // packed table (PK kernels; mgcn_spmm_xw_fwd_packed): X unused
   const uint32_t *pk;
   uint32_t pk_bytes, pk_rbits, pk_head;
   uint32_t pk_base[64];
 };
 
-template <int U, bool PK = false>
+// DYN: the last rounds' chunks are claimed from a global counter instead of
+// falling to workgroup c mod grid.  The workgroups of a launch do not run at
+// one speed (their exit times spread over ~10 % of the kernel, uncorrelated
+// with their slot counts: profiles/balance/tail_before.json), and the kernel
+// ends with the slowest; with the tail claimed, the fast ones take more of it.
+// Every chunk's rows are computed as before, whoever runs it: Y, Z and the
+// mask words keep their bits.  Chunks b + i grid (i < n_my, the rounds before
+// dyn_first) are static; chunk index i >= n_my of a workgroup is dyn_first +
+// a ticket.
+// The next chunk is always known, so that the metadata prefetch two rows
+// ahead keeps its target: wave 0 draws a ticket at the end of phase A of
+// iteration j, posts it (a global mailbox word of the workgroup; LDS is full)
+// at the end of phase B, and every wave reads it after the barrier of
+// iteration j + 1 -- chunk index j + 3.
+template <int U, bool PK = false, bool DYN = false>
 __global__ __launch_bounds__(kXwThreads, 2 * kXwPerCU) void spmm_xw_fwd_kernel(const XwArgs a) {
+  static_assert(!(DYN && PK), "the dynamic claim serves the dense forward");
   __shared__ __attribute__((aligned(16))) char lds[kXfLds];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -626,9 +666,20 @@ __global__ __launch_bounds__(kXwThreads, 2 * kXwPerCU) void spmm_xw_fwd_kernel(c
     }
   };
 
-  const int64_t n_my = my_chunks(n_chunks);
+  // static chunks of this workgroup: all of its round robin, or (DYN) the
+  // rounds before dyn_first (a multiple of the grid, >= 3 rounds)
+  const int64_t n_my = my_chunks(DYN ? a.dyn_first : n_chunks);
   const RowSeq seq{(int64_t)blockIdx.x * kXwRows + 2 * wave + grp, (int64_t)gridDim.x * kXwRows,
                    a.n_rows};
+  XTAIL_ENTRY(0);
+  // DYN: chunk index it + 1 of this workgroup (-1: none; 32-bit: scalar
+  // registers are short), uniform
+  auto stat_chunk = [&](int i) -> int {
+    return i < (int)n_my ? (int)(blockIdx.x + i * gridDim.x) : -1;
+  };
+  int c1 = stat_chunk(1);
+  // row 16 p + 2 wave + grp of chunk c
+  auto dyn_row = [&](int c, int p) { return (int64_t)c * kXwRows + 16 * p + 2 * wave + grp; };
   RowMeta cur, nxt;
   meta_rowptr(a.rowptr, seq.row(0), seq.row(0) < a.n_rows, cur);
   if constexpr (PK) {
@@ -639,7 +690,8 @@ __global__ __launch_bounds__(kXwThreads, 2 * kXwPerCU) void spmm_xw_fwd_kernel(c
   }
   meta_rowptr(a.rowptr, seq.row(1), seq.row(1) < a.n_rows, nxt);
   int it = 0;
-  for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x, ++it) {
+  int prev = -1;  // DYN: the chunk whose rows are staged
+  for (int64_t chunk = blockIdx.x; DYN ? chunk >= 0 : chunk < n_chunks; ++it) {
     char *buf = lds + (it & 1) * kXfBuf;
     float *stage = reinterpret_cast<float *>(lds + kXfStageOff + (it & 1) * kXfStage);
 
@@ -653,8 +705,8 @@ __global__ __launch_bounds__(kXwThreads, 2 * kXwPerCU) void spmm_xw_fwd_kernel(c
       else
         meta_first(a.col, a.w, gl, nxt);
       RowMeta nn;
-      const int64_t r2 = seq.row(k + 2);
-      meta_rowptr(a.rowptr, r2, r2 < a.n_rows && k + 2 < 2 * n_my, nn);
+      const int64_t r2 = DYN ? dyn_row(c1, p) : seq.row(k + 2);
+      meta_rowptr(a.rowptr, r2, r2 < a.n_rows && (DYN ? c1 >= 0 : k + 2 < 2 * n_my), nn);
       float acc[4];
       if constexpr (PK)
         gather_row_meta_pk<U>(pk, a.col, a.w, cur, nxt, gl, grp, acc, hh);
@@ -680,11 +732,25 @@ __global__ __launch_bounds__(kXwThreads, 2 * kXwPerCU) void spmm_xw_fwd_kernel(c
       cur = nxt;
       nxt = nn;
     }
+    // DYN: a ticket for chunk index it + 3 (past the static rounds), drawn
+    // here so that its round trip runs under the barrier and phase B
+    uint32_t ticket = 0;
+    const bool draw = DYN && wave == 0 && it + 3 >= (int)n_my;
+    if constexpr (DYN)
+      if (draw && lane == 0)
+        ticket = __hip_atomic_fetch_add(a.claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     // the previous chunk's output rows (staged before this barrier) go out
     if (it > 0)
-      flush(chunk - gridDim.x, reinterpret_cast<const float *>(lds + kXfStageOff +
-                                                                ((it + 1) & 1) * kXfStage));
+      flush(DYN ? prev : chunk - gridDim.x,
+            reinterpret_cast<const float *>(lds + kXfStageOff + ((it + 1) & 1) * kXfStage));
+    // DYN: the ticket posted in iteration it - 1 (before this barrier)
+    int posted = 0;
+    const bool take = DYN && it + 2 >= (int)n_my && it > 0;
+    if constexpr (DYN)
+      if (take)
+        posted = __hip_atomic_load(a.mail + 2 * blockIdx.x + ((it + 1) & 1), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);
 
     // ---- Phase B: Y = Z W (+ b), ReLU -> staging tile ----------------------
     f32x4_t acc2[2];
@@ -703,12 +769,29 @@ __global__ __launch_bounds__(kXwThreads, 2 * kXwPerCU) void spmm_xw_fwd_kernel(c
         if (a.relu) v = (v < 0.0f) ? 0.0f : v;
         stage[(16 * t + 4 * g4 + r) * kXwF + ncol] = v;
       }
+    if constexpr (DYN) {
+      if (draw && lane == 0)
+        __hip_atomic_store(a.mail + 2 * blockIdx.x + (it & 1), (int)ticket, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+      // chunk index it + 2: static, or dyn_first + the ticket while chunks last
+      int c2 = stat_chunk(it + 2);
+      if (take) {
+        const uint32_t c = (uint32_t)a.dyn_first + (uint32_t)__builtin_amdgcn_readfirstlane(posted);
+        c2 = c < (uint32_t)n_chunks ? (int)c : -1;
+      }
+      prev = (int)chunk;
+      chunk = c1;
+      c1 = c2;
+    } else {
+      chunk += gridDim.x;
+    }
   }
   if (it > 0) {
     __syncthreads();
-    flush(blockIdx.x + (int64_t)(it - 1) * gridDim.x,
+    flush(DYN ? prev : blockIdx.x + (int64_t)(it - 1) * gridDim.x,
           reinterpret_cast<const float *>(lds + kXfStageOff + ((it + 1) & 1) * kXfStage));
   }
+  XTAIL_EXIT(0, it);
 }
 
 // ---------------------------------------------------------------------------
@@ -1087,6 +1170,37 @@ int launch_xw(const XwArgs &a, hipStream_t s) {
   return check_launch("spmm_xw_fwd_kernel");
 }
 
+// mgcn_set_option("xw_dyn_rounds"): the forward's last rounds claimed from a
+// counter (spmm_xw_fwd_kernel DYN; 0: every chunk static)
+int g_xw_dyn_rounds = 8;
+constexpr size_t kXwDynMailOff = 256;  // workspace: the counter, then [grid][2] mailbox words
+
+size_t xw_dyn_workspace_bytes() { return kXwDynMailOff + align_up((size_t)xw_grid() * 8, 256); }
+
+// The dynamic-claim forward where it applies: the default unroll, a
+// workspace, and static rounds left (>= 8, the kernel needs 3) before the
+// claimed ones; returns false (nothing launched) otherwise.
+bool launch_xw_dyn(XwArgs &a, void *workspace, size_t workspace_bytes, hipStream_t s, int *rc) {
+  const int64_t n_chunks = (a.n_rows + kXwRows - 1) / kXwRows;
+  const int64_t grid = xw_grid();
+  const int64_t rounds = n_chunks / grid;
+  if (g_xw_dyn_rounds <= 0 || g_xw_unroll != 5 || workspace == nullptr ||
+      reinterpret_cast<uintptr_t>(workspace) % 4 != 0 || workspace_bytes < xw_dyn_workspace_bytes() || rounds < g_xw_dyn_rounds + 8 ||
+      n_chunks >= (int64_t(1) << 30))
+    return false;
+  a.dyn_first = (int32_t)((rounds - g_xw_dyn_rounds) * grid);
+  a.claim = static_cast<uint32_t *>(workspace);
+  a.mail = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + kXwDynMailOff);
+  if (hipMemsetAsync(a.claim, 0, sizeof(uint32_t), s) != hipSuccess) {
+    *rc = check_launch("hipMemsetAsync");
+    return true;
+  }
+  hipLaunchKernelGGL((spmm_xw_fwd_kernel<5, false, true>), dim3((unsigned)grid), dim3(kXwThreads),
+                     0, s, a);
+  *rc = check_launch("spmm_xw_fwd_kernel");
+  return true;
+}
+
 template <int U, bool DX, int EPI, bool MAXM, bool DW = true, bool PK = false>
 int launch_xb(const XbArgs &a, int grid, hipStream_t s) {
   hipLaunchKernelGGL((spmm_xw_bwd_kernel<U, DX, EPI, MAXM, DW, PK>), dim3((unsigned)grid),
@@ -1241,6 +1355,7 @@ __global__ __launch_bounds__(kBsThreads) void spmm_xw_bwd_ws_kernel(const XbsArg
   const int64_t n_chunks = (a.n_rows + kXwRows - 1) / kXwRows;
   const int64_t n_my = my_chunks(n_chunks);
   auto chunk_of = [&](int64_t i) { return (int64_t)blockIdx.x + i * gridDim.x; };
+  XTAIL_ENTRY(1);
   auto rows_in = [&](int64_t c) -> uint32_t {
     const int64_t r = a.n_rows - c * kXwRows;
     return (uint32_t)(r <= 0 ? 0 : r >= kXwRows ? kXwRows : r);
@@ -1572,6 +1687,7 @@ __global__ __launch_bounds__(kBsThreads) void spmm_xw_bwd_ws_kernel(const XbsArg
       A.hcs_partial[(int64_t)blockIdx.x * kXwF + f] = s;
     }
   }
+  XTAIL_EXIT(1, n_my);
 }
 
 int g_xw_ws_full = 1;  // mgcn_set_option("xw_ws_full"): the warp-specialised dW + dX adjoint (DWS)
@@ -1667,6 +1783,15 @@ int xw_set_ws(const char *name, int value) {
   return unroll(g_bs_full_unroll, {4, 5, 6});  // "xw_ws_full_unroll"
 }
 
+int xw_set_dyn_rounds(int value) {
+  if (value < 0 || value > 64) {
+    set_error("xw_dyn_rounds must be in 0 .. 64 (0: no dynamic claim)");
+    return MGCN_EINVAL;
+  }
+  g_xw_dyn_rounds = value;
+  return MGCN_OK;
+}
+
 int xw_set_unroll(int value) {
   if (value != 4 && value != 5 && value != 6 && value != 8) {
     set_error("spmm_xw_unroll must be 4, 5, 6 or 8 (5 / 6: the forward only)");
@@ -1692,6 +1817,7 @@ extern "C" int mgcn_spmm_xw_bwd_full_supported(int32_t F_in, int32_t F_out) {
 }
 
 extern "C" size_t mgcn_spmm_xw_fwd_workspace_bytes(int32_t F_in, int32_t F_out) {
+  if (F_in == kXwF && F_out == kXwF) return xw_dyn_workspace_bytes();
   return F_in == 256 && F_out == 256 ? xw_wide_workspace_bytes(false) : 0;
 }
 
@@ -1764,6 +1890,9 @@ extern "C" int mgcn_spmm_xw_fwd(int64_t n_rows, int64_t n_cols, int32_t F_in, in
   a.mean = reduce == MGCN_REDUCE_MEAN;
   a.relu = relu != 0;
   hipStream_t s = as_stream(stream);
+  // (without the workspace -- callers from before it existed -- every chunk is static)
+  int rc = MGCN_OK;
+  if (launch_xw_dyn(a, workspace, workspace_bytes, s, &rc)) return rc;
   return g_xw_unroll == 4 ? launch_xw<4>(a, s)
        : g_xw_unroll == 5 ? launch_xw<5>(a, s)
        : g_xw_unroll == 6 ? launch_xw<6>(a, s)
@@ -1944,6 +2073,18 @@ extern "C" int mgcn_spmm_xw_bwd_hcs(int64_t n_rows, int64_t n_cols, const int64_
                      ldx, W, ldw, dW, lddw, accumulate, dX, lddx, relu_mask, row_div, colsum,
                      nullptr, nullptr, dy_colsum, workspace, workspace_bytes, stream);
 }
+
+#if MGCN_EXPERIMENT
+// [2][1024][4] ticks (g_tail above) to `host`, then cleared for the next launch
+extern "C" int mgcn_debug_xw_tail(unsigned long long *host) {
+  MGCN_HIP_TRY(hipDeviceSynchronize());
+  if (host != nullptr)
+    MGCN_HIP_TRY(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_tail), sizeof(g_tail)));
+  static const unsigned long long zero[2][kTailMaxWg][4] = {};
+  MGCN_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_tail), zero, sizeof(zero)));
+  return MGCN_OK;
+}
+#endif
 
 #ifdef MGCN_XW_PROFILE
 extern "C" int mgcn_debug_xw_prof(unsigned long long *host) {
