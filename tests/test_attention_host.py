@@ -1,9 +1,11 @@
 """CPU-only checks of the attention node model's host layer and C ABI boundary
 (no GPU compute): module surface against the reference's, argument validation
-before any launch."""
+before any launch; the GPU tests' torch restatement against the reference's
+fp64 fixtures."""
 import pytest
 import torch
 
+from attention_ref import FIXTURES, ref_run
 from conftest import load_golden
 
 
@@ -79,6 +81,28 @@ def test_cpu_input_raises():
         NodeModelAttention(4, 6, nheads=2)(x, ei)
     with pytest.raises(mgcn.MgcnError, match="HIP device"):
         GCNLayer(4, 6, nodemodel='attention', nheads=2)(x, ei)
+
+
+@pytest.mark.parametrize("name", sorted(FIXTURES))
+def test_restatement_agrees_with_reference_fixture(name):
+    """The torch restatement (attention_ref.att_ref), the yardstick of every
+    random GPU case, run in fp64 on a fixture's own x / parameters / edges /
+    dY against the reference's fp64 results: max|r64 - t64| <= 1e-12 max|t64|.
+    Measured 3.9e-16 .. 6.9e-16 relative; 1e-12 leaves room for another BLAS's
+    summation order and is five orders below the fp32 error (2.4e-7 .. 3.8e-7)
+    that the GPU bound rests on."""
+    fin, fout, H, combine, adir, act, bias = FIXTURES[name]
+    z = {k: torch.from_numpy(v) for k, v in load_golden(name).items()}
+    assert z["p_weight"].shape[0] == fin and z["dY"].shape[1] == fout
+    r64 = ref_run(z["x"], z["p_weight"], z["p_att_weight"], z["p_bias"] if bias else None,
+                  z["edge_index"], z["dY"], H, combine, adir, act, torch.float64)
+    for k in ("y", "alpha", "dx", "dW", "datt") + (("db",) if bias else ()):
+        t64 = z[k + "64"]
+        assert r64[k].dtype == torch.float64 and r64[k].shape == t64.shape, k
+        err = (r64[k] - t64).abs().max().item()
+        scale = t64.abs().max().item()
+        print(f"{name}.{k}: restatement err {err:.3e}  max|t64| {scale:.3e}")
+        assert err <= 1e-12 * scale, f"{name}.{k}: {err:.3e} > 1e-12 * {scale:.3e}"
 
 
 def _calls(lib, n, nnz, H, C):
