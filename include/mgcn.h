@@ -906,6 +906,77 @@ int mgcn_att_dst_fold(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const i
                       const float *dz, const float *a, float *ds_dst, float *dHp, int64_t lddh,
                       void *stream);
 
+/* -------------------------------------------- hard attention node model */
+
+/*
+ * Gumbel-softmax / argmax hard attention: the message passing of
+ * NodeModelHardAttention (src/gcn_meta/models/graph_hard_attention.py:70-136)
+ * and of VotePoolLayer (gpool_hard_attention.py:214-275).  Added under ABI 22
+ * as the attention entries were (backward-compatible: the version stays 22);
+ * the mgcn_att_* entries are unchanged and share their device code with these
+ * through template parameters.  Shapes, limits, error behaviour and the
+ * determinism guarantees are those of the attention entries above.
+ *
+ * Training: the logit of slot k is  l_k = (act(z_k) + noise_k) / T  (an fp32
+ * add, then an fp32 divide), the softmax over the row is the one above with l
+ * in the place of e.  noise is [nnz, H] in the slot order of the view the
+ * call walks, NULL = zeros.  temperature must be > 0 (else MGCN_EINVAL).  With
+ * noise == NULL and T == 1 every entry returns the bits of its mgcn_att_*
+ * counterpart.
+ */
+int mgcn_hatt_fwd(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr,
+                  const int32_t *col, const float *s_row, const float *s_col, int act,
+                  const float *noise, float temperature, const float *alpha_in,
+                  const float *mask, const float *Hp, int64_t ldh, float *Y, int64_t ldy,
+                  float *alpha, void *stream);
+
+int mgcn_hatt_edge_softmax(int64_t n_rows, int64_t nnz, int32_t H, const int64_t *rowptr,
+                           const int32_t *col, const float *s_row, const float *s_col, int act,
+                           const float *noise, float temperature, float *alpha, void *stream);
+
+/* mgcn_att_bwd_dst / mgcn_att_bwd_src with the 1 / T of the logit:
+ *   dz_k = alpha_k (dalpha_k - sum_row alpha dalpha) / T  act'(z_k).
+ * act' depends on z alone, so the noise is not an argument.  ds, the dHp
+ * terms, mgcn_att_dst_fold for 'out' and da are as for soft attention. */
+int mgcn_hatt_bwd_dst(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr,
+                      const int32_t *col, const float *Hp, int64_t ldh, const float *dY,
+                      int64_t lddy, const float *alpha, const float *mask, const float *s_row,
+                      const float *s_col, int act, int softmax, float temperature, float *dz,
+                      float *ds_row, void *stream);
+
+int mgcn_hatt_bwd_src(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr_t,
+                      const int32_t *col_t, const int32_t *slot_map, const float *dY,
+                      int64_t lddy, const float *alpha, const float *mask, float *dz,
+                      const float *s_row, const float *s_col, int act, int softmax,
+                      float temperature, const float *a, const float *ds_dst, float *ds_src,
+                      float *dHp, int64_t lddh, void *stream);
+
+/*
+ * Eval: the winner of every (row, head) of any view (groups = rows) among
+ * l_k = act(z_k) + noise_k  (z = s_row[row] + s_col[col]; noise NULL = none;
+ * no temperature).  The tie rule is torch_scatter 1.x's CPU scan: start from
+ * -1e16f, `l >= best` replaces the winner, so the last slot in slot (COO)
+ * order among equal maxima wins; a value below -1e16f or a NaN never wins; an
+ * empty row has no winner.  alpha [nnz, H] in the view's slot order receives
+ * the one-hot (every entry is written, 1.0f or 0.0f), winner [n_rows, H] the
+ * winning slot or -1.
+ */
+int mgcn_hatt_select(int64_t n_rows, int64_t nnz, int32_t H, const int64_t *rowptr,
+                     const int32_t *col, const float *s_row, const float *s_col, int act,
+                     const float *noise, float *alpha, int32_t *winner, void *stream);
+
+/*
+ * Y[row,h,:] = sum_k alpha_k[h] Hp[col_k,h,:] over the fwd view, alpha [nnz, H]
+ * in fwd slot order, terms added in slot order.  The feature row of a slot
+ * whose H coefficients are all zero is not loaded (a wave-uniform test).  For
+ * finite Hp the result is bit for bit mgcn_att_fwd(alpha_in = alpha, mask =
+ * NULL).  Non-finite Hp is outside the contract: a skipped 0 * inf stays 0
+ * where the reference's dense product would give NaN.
+ */
+int mgcn_hatt_gather(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr,
+                     const int32_t *col, const float *alpha, const float *Hp, int64_t ldh,
+                     float *Y, int64_t ldy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,95 +32,15 @@
 //
 // Roofline (forward, 'in'): 8 (N + 1) rowptr + nnz (4 col + 4 H C row + 4 H
 // s_src + 4 H alpha) + 4 N H C (Y) + 4 N H (s_dst) bytes.
+//
+// The lane-layout helpers, the softmax + gather kernel and the two adjoint
+// kernels live in attention.h, shared with hard_attention.hip; the scores and
+// fold kernels and the soft C entries are here.
 
-#include "mgcn_internal.h"
+#include "attention.h"
 
 namespace mgcn {
 namespace {
-
-constexpr int kAttWaves = 4;
-constexpr int kAttThreads = 64 * kAttWaves;
-
-__device__ inline float att_act(float z, int act) {
-  if (act == MGCN_ATT_ACT_LRELU) return z > 0.0f ? z : __fmul_rn(z, 0.2f);
-  if (act == MGCN_ATT_ACT_RELU) return z > 0.0f ? z : 0.0f;
-  return z;
-}
-
-// d act / dz as torch's leaky_relu / relu backward take it (z == 0: the
-// negative side)
-__device__ inline float att_act_grad(float z, int act) {
-  if (act == MGCN_ATT_ACT_LRELU) return z > 0.0f ? 1.0f : 0.2f;
-  if (act == MGCN_ATT_ACT_RELU) return z > 0.0f ? 1.0f : 0.0f;
-  return 1.0f;
-}
-
-// Flat layout: the total over the lanes of one head (lane % H), left in every
-// lane of that head.  Lanes >= (64 / H) H pass 0.
-__device__ inline float head_sum(float v, int H, int h) {
-  if ((H & (H - 1)) == 0) {
-    for (int off = 32; off >= H; off >>= 1) v = __fadd_rn(v, __shfl_xor(v, off, 64));
-    return v;
-  }
-  float acc = 0.0f;
-  for (int g = 0; g < 64 / H; ++g) acc = __fadd_rn(acc, __shfl(v, g * H + h, 64));
-  return acc;
-}
-
-__device__ inline float head_max(float v, int H, int h) {
-  if ((H & (H - 1)) == 0) {
-    for (int off = 32; off >= H; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-  }
-  float acc = v;
-  for (int g = 0; g < 64 / H; ++g) acc = fmaxf(acc, __shfl(v, g * H + h, 64));
-  return acc;
-}
-
-// Feature layout: lane hh (< H) receives sum_{f of head hh} prod[f]; every
-// lane calls it.  Own products in i order, then the xor-butterfly, head after
-// head.  C a power of two <= 64: the heads are aligned segments of C lanes
-// (head of (lane, i) = lane / C + i 64 / C), so one segmented butterfly per i
-// sums all of them at once and lane hh fetches its head's total.
-template <int FPL>
-__device__ inline float head_dots(const float (&prod)[FPL], const int (&hf)[FPL], int H, int C,
-                                  int lane) {
-  float mine = 0.0f;
-  if ((C & (C - 1)) == 0 && C <= 64) {
-    const int hpi = 64 / C;
-#pragma unroll
-    for (int i = 0; i < FPL; ++i) {
-      float p = prod[i];
-      for (int off = C >> 1; off >= 1; off >>= 1) p = __fadd_rn(p, __shfl_xor(p, off, 64));
-      const float v = __shfl(p, (lane % hpi) * C, 64);
-      if (lane / hpi == i) mine = v;
-    }
-    return mine;
-  }
-  for (int hh = 0; hh < H; ++hh) {
-    float p = 0.0f;
-#pragma unroll
-    for (int i = 0; i < FPL; ++i) p = __fadd_rn(p, hf[i] == hh ? prod[i] : 0.0f);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p = __fadd_rn(p, __shfl_xor(p, off, 64));
-    if (lane == hh) mine = p;
-  }
-  return mine;
-}
-
-template <int FPL>
-__device__ inline void feature_heads(int (&hf)[FPL], int lane, int HC, int C) {
-#pragma unroll
-  for (int i = 0; i < FPL; ++i) {
-    const int f = lane + 64 * i;
-    hf[i] = f < HC ? f / C : 0;
-  }
-}
-
-template <int FPL>
-constexpr int gather_unroll() {
-  return FPL <= 4 ? 4 : 2;
-}
 
 // ------------------------------------------------------------------ scores
 struct ScoreArgs {
@@ -166,288 +86,6 @@ __global__ __launch_bounds__(kAttThreads) void att_scores_kernel(ScoreArgs a) {
   }
 }
 
-// ----------------------------------------------- softmax + weighted gather
-struct FwdArgs {
-  int64_t n_rows;
-  int H, C, act;
-  const int64_t *rowptr;
-  const int32_t *col;
-  const float *s_row, *s_col, *alpha_in, *mask, *Hp;
-  int64_t ldh;
-  float *Y;
-  int64_t ldy;
-  float *alpha;
-};
-
-// GATHER: Y rows as well (mgcn_att_fwd); else alpha only (mgcn_edge_softmax)
-template <int FPL, bool GATHER>
-__global__ __launch_bounds__(kAttThreads) void att_fwd_kernel(FwdArgs a) {
-  constexpr int U = gather_unroll<FPL>();
-  const int lane = threadIdx.x & 63;
-  const int64_t wave0 = blockIdx.x * (int64_t)kAttWaves + (threadIdx.x >> 6);
-  const int64_t nwaves = (int64_t)gridDim.x * kAttWaves;
-  const int H = a.H, G = 64 / a.H, HC = a.H * a.C;
-  const int h = lane % H, kl = lane / H;
-  const bool live = lane < G * H;
-  int hf[FPL];
-  feature_heads<FPL>(hf, lane, HC, GATHER ? a.C : 1);
-  for (int64_t row = wave0; row < a.n_rows; row += nwaves) {
-    const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
-    float m = -1e16f, denom = 1.0f, sr = 0.0f;
-    if (a.alpha_in == nullptr) {
-      sr = a.s_row[row * H + h];
-      for (int64_t k0 = beg; k0 < end; k0 += G) {
-        const int64_t k = k0 + kl;
-        if (live && k < end)
-          m = fmaxf(m, att_act(__fadd_rn(sr, a.s_col[(int64_t)a.col[k] * H + h]), a.act));
-      }
-      m = head_max(m, H, h);
-      float sum = 0.0f;
-      for (int64_t k0 = beg; k0 < end; k0 += G) {
-        const int64_t k = k0 + kl;
-        if (live && k < end) {
-          const float e = att_act(__fadd_rn(sr, a.s_col[(int64_t)a.col[k] * H + h]), a.act);
-          sum = __fadd_rn(sum, expf(__fsub_rn(e, m)));
-        }
-      }
-      denom = __fadd_rn(head_sum(sum, H, h), 1e-16f);
-    }
-    float acc[FPL];
-#pragma unroll
-    for (int i = 0; i < FPL; ++i) acc[i] = 0.0f;
-    for (int64_t k0 = beg; k0 < end; k0 += G) {
-      const int64_t k = k0 + kl;
-      float al = 0.0f;  // alpha' of this lane's (slot, head)
-      if (live && k < end) {
-        const int64_t idx = k * H + h;
-        if (a.alpha_in != nullptr) {
-          al = a.alpha_in[idx];
-        } else {
-          const float e = att_act(__fadd_rn(sr, a.s_col[(int64_t)a.col[k] * H + h]), a.act);
-          al = __fdiv_rn(expf(__fsub_rn(e, m)), denom);
-          a.alpha[idx] = al;
-        }
-        if (a.mask != nullptr) al = __fmul_rn(al, a.mask[idx]);
-      }
-      if (GATHER) {
-        const int ns = (int)(end - k0 < G ? end - k0 : G);
-        for (int kk = 0; kk < ns; kk += U) {
-          float hp[U][FPL];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const bool on = kk + u < ns;
-            const int64_t c = on ? __builtin_amdgcn_readfirstlane(a.col[k0 + kk + u]) : 0;
-#pragma unroll
-            for (int i = 0; i < FPL; ++i) {
-              const int f = lane + 64 * i;
-              hp[u][i] = (on && f < HC) ? a.Hp[c * a.ldh + f] : 0.0f;
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            if (kk + u < ns) {
-#pragma unroll
-              for (int i = 0; i < FPL; ++i) {
-                const float w = __shfl(al, (kk + u) * H + hf[i], 64);
-                acc[i] = __fadd_rn(acc[i], __fmul_rn(w, hp[u][i]));
-              }
-            }
-          }
-        }
-      }
-    }
-    if (GATHER) {
-#pragma unroll
-      for (int i = 0; i < FPL; ++i) {
-        const int f = lane + 64 * i;
-        if (f < HC) a.Y[row * a.ldy + f] = acc[i];
-      }
-    }
-  }
-}
-
-// ------------------------------------------------- adjoint, by destination
-struct BwdDstArgs {
-  int64_t n_rows;
-  int H, C, act, softmax;
-  const int64_t *rowptr;
-  const int32_t *col;
-  const float *Hp;
-  int64_t ldh;
-  const float *dY;
-  int64_t lddy;
-  const float *alpha, *mask, *s_row, *s_col;
-  float *dz, *ds_row;
-};
-
-template <int FPL>
-__global__ __launch_bounds__(kAttThreads) void att_bwd_dst_kernel(BwdDstArgs a) {
-  constexpr int U = gather_unroll<FPL>();
-  const int lane = threadIdx.x & 63;
-  const int64_t wave0 = blockIdx.x * (int64_t)kAttWaves + (threadIdx.x >> 6);
-  const int64_t nwaves = (int64_t)gridDim.x * kAttWaves;
-  const int H = a.H, G = 64 / a.H, HC = a.H * a.C;
-  const int h = lane % H, kl = lane / H;
-  const bool live = lane < G * H;
-  int hf[FPL];
-  feature_heads<FPL>(hf, lane, HC, a.C);
-  for (int64_t row = wave0; row < a.n_rows; row += nwaves) {
-    float dy[FPL];
-#pragma unroll
-    for (int i = 0; i < FPL; ++i) {
-      const int f = lane + 64 * i;
-      dy[i] = f < HC ? a.dY[row * a.lddy + f] : 0.0f;
-    }
-    const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
-    float S = 0.0f;  // lane hh < H: sum_k alpha dalpha of head hh
-    for (int64_t k0 = beg; k0 < end; k0 += U) {
-      float hp[U][FPL], ml[U], al[U];  // ml / al: lane hh < H, the slot's mask / alpha of head hh
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bool on = k0 + u < end;
-        const int64_t c = on ? __builtin_amdgcn_readfirstlane(a.col[k0 + u]) : 0;
-#pragma unroll
-        for (int i = 0; i < FPL; ++i) {
-          const int f = lane + 64 * i;
-          hp[u][i] = (on && f < HC) ? a.Hp[c * a.ldh + f] : 0.0f;
-        }
-        const bool mine_on = on && lane < H;
-        ml[u] = (mine_on && a.mask != nullptr) ? a.mask[(k0 + u) * H + lane] : 1.0f;
-        al[u] = (mine_on && a.softmax) ? a.alpha[(k0 + u) * H + lane] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (k0 + u < end) {
-#pragma unroll
-          for (int i = 0; i < FPL; ++i) hp[u][i] = __fmul_rn(dy[i], hp[u][i]);
-          const float mine = head_dots<FPL>(hp[u], hf, H, a.C, lane);
-          if (lane < H) {
-            const float d = a.mask != nullptr ? __fmul_rn(mine, ml[u]) : mine;
-            a.dz[(k0 + u) * H + lane] = d;
-            if (a.softmax) S = __fadd_rn(S, __fmul_rn(al[u], d));
-          }
-        }
-      }
-    }
-    if (a.softmax) {
-      // the dalpha entries above are re-read by other lanes of this wave
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      const float Sh = __shfl(S, h, 64);
-      const float sr = a.s_row[row * H + h];
-      float part = 0.0f;
-      for (int64_t k0 = beg; k0 < end; k0 += G) {
-        const int64_t k = k0 + kl;
-        if (live && k < end) {
-          const int64_t idx = k * H + h;
-          const float z = __fadd_rn(sr, a.s_col[(int64_t)a.col[k] * H + h]);
-          const float de = __fmul_rn(a.alpha[idx], __fsub_rn(a.dz[idx], Sh));
-          const float v = __fmul_rn(de, att_act_grad(z, a.act));
-          a.dz[idx] = v;
-          part = __fadd_rn(part, v);
-        }
-      }
-      const float tot = head_sum(part, H, h);
-      if (lane < H) a.ds_row[row * H + lane] = tot;
-    }
-  }
-}
-
-// ------------------------------------------------------ adjoint, by source
-struct BwdSrcArgs {
-  int64_t n_rows;
-  int H, C, act, softmax;
-  const int64_t *rowptr;
-  const int32_t *col, *slot;
-  const float *dY;
-  int64_t lddy;
-  const float *alpha, *mask;
-  float *dz;
-  const float *s_row, *s_col, *a, *ds_dst;
-  float *ds_src, *dHp;
-  int64_t lddh;
-};
-
-template <int FPL>
-__global__ __launch_bounds__(kAttThreads) void att_bwd_src_kernel(BwdSrcArgs a) {
-  constexpr int U = gather_unroll<FPL>();
-  const int lane = threadIdx.x & 63;
-  const int64_t wave0 = blockIdx.x * (int64_t)kAttWaves + (threadIdx.x >> 6);
-  const int64_t nwaves = (int64_t)gridDim.x * kAttWaves;
-  const int H = a.H, G = 64 / a.H, HC = a.H * a.C;
-  const int h = lane % H, kl = lane / H;
-  const bool live = lane < G * H;
-  int hf[FPL];
-  feature_heads<FPL>(hf, lane, HC, a.C);
-  for (int64_t row = wave0; row < a.n_rows; row += nwaves) {
-    const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
-    float acc[FPL];
-#pragma unroll
-    for (int i = 0; i < FPL; ++i) acc[i] = 0.0f;
-    // lane hh < H: softmax ? sum_k alpha dalpha : sum_k dz (= ds_src) of head hh
-    float S = 0.0f;
-    for (int64_t k0 = beg; k0 < end; k0 += U) {
-      float dy[U][FPL], w[U][FPL], dzl[U], all[U];  // dzl / all: lane hh < H, the slot's dz / alpha
-      int64_t fs[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bool on = k0 + u < end;
-        const int64_t c = on ? __builtin_amdgcn_readfirstlane(a.col[k0 + u]) : 0;
-        fs[u] = on ? __builtin_amdgcn_readfirstlane(a.slot[k0 + u]) : 0;
-#pragma unroll
-        for (int i = 0; i < FPL; ++i) {
-          const int f = lane + 64 * i;
-          const bool ld = on && f < HC;
-          dy[u][i] = ld ? a.dY[c * a.lddy + f] : 0.0f;
-          w[u][i] = ld ? a.alpha[fs[u] * H + hf[i]] : 0.0f;
-          if (a.mask != nullptr) w[u][i] = ld ? __fmul_rn(w[u][i], a.mask[fs[u] * H + hf[i]]) : 0.0f;
-        }
-        const bool mine_on = on && lane < H;
-        dzl[u] = mine_on ? a.dz[fs[u] * H + lane] : 0.0f;
-        all[u] = (mine_on && a.softmax) ? a.alpha[fs[u] * H + lane] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (k0 + u < end) {
-#pragma unroll
-          for (int i = 0; i < FPL; ++i) acc[i] = __fadd_rn(acc[i], __fmul_rn(w[u][i], dy[u][i]));
-          if (lane < H) S = __fadd_rn(S, a.softmax ? __fmul_rn(all[u], dzl[u]) : dzl[u]);
-        }
-      }
-    }
-    float dsv = S;  // lane hh < H: ds_src[row, hh]
-    if (a.softmax) {
-      const float Sh = __shfl(S, h, 64);
-      const float sr = a.s_row[row * H + h];
-      float part = 0.0f;
-      for (int64_t k0 = beg; k0 < end; k0 += G) {
-        const int64_t k = k0 + kl;
-        if (live && k < end) {
-          const int64_t idx = (int64_t)a.slot[k] * H + h;
-          const float z = __fadd_rn(sr, a.s_col[(int64_t)a.col[k] * H + h]);
-          const float de = __fmul_rn(a.alpha[idx], __fsub_rn(a.dz[idx], Sh));
-          const float v = __fmul_rn(de, att_act_grad(z, a.act));
-          a.dz[idx] = v;
-          part = __fadd_rn(part, v);
-        }
-      }
-      dsv = head_sum(part, H, h);
-    }
-    if (lane < H) a.ds_src[row * H + lane] = dsv;
-#pragma unroll
-    for (int i = 0; i < FPL; ++i) {
-      const int f = lane + 64 * i;
-      const int hh = hf[i], c = f - hf[i] * a.C;
-      const float ds = __shfl(dsv, hh, 64);
-      if (f < HC) {
-        float v = __fadd_rn(acc[i], __fmul_rn(ds, a.a[(int64_t)hh * 2 * a.C + c]));
-        if (a.ds_dst != nullptr)
-          v = __fadd_rn(v, __fmul_rn(a.ds_dst[row * H + hh], a.a[(int64_t)hh * 2 * a.C + a.C + c]));
-        a.dHp[row * a.lddh + f] = v;
-      }
-    }
-  }
-}
-
 // ------------------------------- 'out': ds_dst and its term of dHp, by row
 __global__ __launch_bounds__(kAttThreads) void att_dst_fold_kernel(
     int64_t n_rows, int H, int C, const int64_t *__restrict__ rowptr, const float *__restrict__ dz,
@@ -480,39 +118,10 @@ __global__ __launch_bounds__(kAttThreads) void att_dst_fold_kernel(
   }
 }
 
-unsigned att_grid(int64_t n_rows) {
-  int64_t blocks = (n_rows + kAttWaves - 1) / kAttWaves;
-  if (blocks > 4096) blocks = 4096;
-  return (unsigned)blocks;
-}
-
-#define ATT_DISPATCH(HC, CALL)          \
-  do {                                  \
-    const int fpl_ = ((HC) + 63) / 64;  \
-    if (fpl_ <= 1) CALL(1);             \
-    else if (fpl_ <= 2) CALL(2);        \
-    else if (fpl_ <= 4) CALL(4);        \
-    else if (fpl_ <= 8) CALL(8);        \
-    else CALL(16);                      \
-  } while (0)
-
 }  // namespace
 }  // namespace mgcn
 
 using namespace mgcn;
-
-// the supported range, checked on the host before any launch
-#define ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C)                                              \
-  do {                                                                                        \
-    MGCN_REQUIRE((n_rows) >= 0 && (nnz) >= 0, fn ": negative size");                          \
-    MGCN_REQUIRE((H) >= 1 && (H) <= 16, fn ": need 1 <= H <= 16 (H = %d)", (int)(H));          \
-    MGCN_REQUIRE((C) >= 1 && (int64_t)(H) * (C) <= 1024,                                      \
-                 fn ": need C >= 1 and H C <= 1024 (H = %d, C = %d)", (int)(H), (int)(C));     \
-    MGCN_REQUIRE((int64_t)(nnz) * (H) < ((int64_t)1 << 31), fn ": need nnz H < 2^31");         \
-  } while (0)
-
-#define ATT_ACT_OK(fn, act) \
-  MGCN_REQUIRE((act) >= MGCN_ATT_ACT_NONE && (act) <= MGCN_ATT_ACT_RELU, fn ": bad act %d", act)
 
 extern "C" int mgcn_att_scores(int64_t n, int32_t H, int32_t C, const float *Hp, int64_t ldh,
                                const float *a, float *s_src, float *s_dst, void *stream) {

@@ -31,6 +31,7 @@ _i64 = ctypes.c_int64
 _i32 = ctypes.c_int32
 _int = ctypes.c_int
 _sz = ctypes.c_size_t
+_f32 = ctypes.c_float
 
 # name -> (restype, argtypes); every symbol include/mgcn.h declares
 SIGNATURES = {
@@ -134,6 +135,16 @@ SIGNATURES = {
     "mgcn_att_bwd_src": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                 _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mgcn_att_dst_fold": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mgcn_hatt_fwd": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _int, _vp, _f32, _vp, _vp,
+                             _vp, _i64, _vp, _i64, _vp, _vp]),
+    "mgcn_hatt_edge_softmax": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _f32, _vp,
+                                      _vp]),
+    "mgcn_hatt_bwd_dst": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
+                                 _vp, _vp, _int, _int, _f32, _vp, _vp, _vp]),
+    "mgcn_hatt_bwd_src": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                 _vp, _vp, _int, _int, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mgcn_hatt_select": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "mgcn_hatt_gather": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
 }
 
 class PackedTableC(ctypes.Structure):

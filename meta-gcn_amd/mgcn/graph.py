@@ -151,6 +151,14 @@ class GraphPlan:
     _key_refs: list = field(default_factory=list)
     _slot_map: torch.Tensor | None = None
     _coo: tuple | None = None
+    _last_slot: torch.Tensor | None = None
+
+    def last_edge_slot(self) -> torch.Tensor:
+        """0-d int64 device tensor: the fwd-view slot of COO edge nnz - 1 (the
+        edge hard attention's eval quirk marks), found on first use."""
+        if self._last_slot is None:
+            self._last_slot = (self.fwd.eid[:self.nnz] == self.nnz - 1).nonzero()[0, 0]
+        return self._last_slot
 
     def slot_map(self) -> torch.Tensor:
         """int32 [nnz]: the fwd-view slot of every bwd-view slot (mgcn_slot_map),

@@ -30,6 +30,7 @@ from torch.nn.utils.rnn import pad_sequence
 from . import _lib as L
 from .graph import plan_for
 from .ops import (aggregate_plan, attention_aggregate, gcn_layer, gcn_stack, linear, linear_bias,  # noqa: F401
+                  hard_attention_aggregate,
                   residual_gcn_layer, residual_layer_supported, residual_stack,  # noqa: F401
                   scatter_)
 
@@ -268,10 +269,109 @@ class NodeModelAttention(NodeModelBase):
                     self.att_combine, self.att_dir, self.num_parameters())
 
 
+# ------------------------------------------------- graph_hard_attention.py
+def gumbel_samples(base):
+    """graph_hard_attention.py:12-20: iid Gumbel(0, 1) samples with the size,
+    dtype and device of ``base``.  NodeModelHardAttention.forward calls it
+    through this module global, once, with a float32 [E, nheads] tensor, and
+    reads the result in COO edge order (tests replace the global to replay
+    recorded noise)."""
+    noise = torch.rand(base.size()).to(base)
+    eps = 1e-20
+    noise.add_(eps).log_().neg_()
+    noise.add_(eps).log_().neg_()
+    return noise
+
+
+class NodeModelHardAttention(NodeModelBase):
+    """graph_hard_attention.py:23-163: multi-head hard attention over a
+    node's neighbourhood.  Training is the Gumbel-softmax relaxation (noise
+    and a temperature inside the softmax logits, dropout on the coefficients);
+    eval keeps, per node and head, the single neighbour with the largest score
+    (plus Gumbel noise when ``sample``).  ``x @ W`` runs on
+    :func:`mgcn.ops.linear`, everything after it on
+    :func:`mgcn.ops.hard_attention_aggregate`, which also mirrors the
+    reference's last-edge quirk for nodes without a neighbour.  Head widths
+    follow ``att_combine`` as in :class:`NodeModelAttention`."""
+
+    def __init__(self, in_channels, out_channels, in_edgedim=None, nheads=1, att_act='none',
+                 att_dropout=0, att_combine='cat', att_dir='in', bias=False, temperature=0.1,
+                 sample=False, **kwargs):
+        assert att_act in ['none', 'lrelu', 'relu']
+        assert att_combine in ['cat', 'add', 'mean']
+        assert att_dir in ['in', 'out']
+        super().__init__(in_channels, out_channels, in_edgedim)
+        self.nheads = nheads
+        if att_combine == 'cat':
+            self.out_channels_1head = out_channels // nheads
+            assert self.out_channels_1head * nheads == out_channels, \
+                'out_channels should be divisible by nheads'
+        else:
+            self.out_channels_1head = out_channels
+        self.att_combine = att_combine
+        self.att_dir = att_dir
+        self.att_act_name = att_act
+        self.temperature = temperature
+        self.sample = sample
+        self.weight = Parameter(torch.Tensor(in_channels, self.out_channels_1head * nheads))
+        self.att_weight = Parameter(torch.Tensor(1, nheads, 2 * self.out_channels_1head))
+        self.att_act = activation(att_act)
+        self.att_dropout = nn.Dropout(p=att_dropout)
+        if bias:
+            self.bias = Parameter(torch.Tensor(out_channels))
+        else:
+            self.register_parameter('bias', None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot(self.weight)
+        glorot(self.att_weight)
+        zeros(self.bias)
+
+    def forward(self, x, edge_index, edge_attr=None, deg=None, edge_weight=None, attn_store=None,
+                **kwargs):
+        """'deg' and 'edge_weight' are not used (as in the reference).
+        ``attn_store`` (a list) receives the coefficients that weighted the
+        messages, [E, nheads] in COO edge order, detached: in training the
+        Gumbel-softmax after dropout, in eval the one-hot (with the quirk
+        edge)."""
+        plan = plan_for(edge_index, x.size(0))
+        hp = linear(x, self.weight)
+        noise = mask = None
+        if self.training or self.sample:
+            noise = gumbel_samples(torch.empty(plan.nnz, self.nheads, dtype=torch.float32,
+                                               device=hp.device))
+        if self.training and self.att_dropout.p > 0:
+            mask = nn.functional.dropout(
+                torch.ones(plan.nnz, self.nheads, dtype=torch.float32, device=hp.device),
+                p=self.att_dropout.p, training=True)
+        y, alpha = hard_attention_aggregate(hp, self.att_weight, plan, self.nheads,
+                                            self.att_act_name, self.att_dir, self.temperature,
+                                            training=self.training, noise=noise, edge_mask=mask)
+        if self.att_combine == 'add':
+            y = y.view(-1, self.nheads, self.out_channels_1head).sum(dim=1)
+        elif self.att_combine == 'mean':
+            y = y.view(-1, self.nheads, self.out_channels_1head).mean(dim=1)
+        if self.bias is not None:
+            y = y + self.bias
+        if attn_store is not None:
+            attn_store.append(alpha)
+        return y
+
+    def __repr__(self):
+        return ('{} (in_channels: {}, out_channels: {}, in_edgedim: {}, nheads: {}, '
+                'att_activation: {},att_dropout: {}, att_combine: {}, att_dir: {}, '
+                'temperature: {} | number of parameters: {})').format(
+                    self.__class__.__name__, self.in_channels, self.out_channels,
+                    self.in_edgedim, self.nheads, self.att_act, self.att_dropout.p,
+                    self.att_combine, self.att_dir, self.temperature, self.num_parameters())
+
+
 # ------------------------------------------------------ gcn_multi_kernel.py
 class GCNMultiKernel(nn.Module):
     """gcn_multi_kernel.py:9-114.  The 'additive' and 'attention' node models
-    run on this engine; the sampling-based hard attention is out of scope."""
+    run on this engine; 'hardattention' is not registered here yet
+    (:class:`NodeModelHardAttention` exists and is used directly)."""
 
     nodemodel_dict = {'additive': NodeModelAdditive, 'attention': NodeModelAttention}
 
@@ -580,5 +680,6 @@ class GCNModel(nn.Module):
 
 
 __all__ = ["glorot", "zeros", "Identity", "activation", "scatter_", "Linear", "NodeModelBase",
-           "NodeModelAdditive", "NodeModelAttention", "GCNMultiKernel", "GCNLayer", "GCNStack", "GCNModel"]
+           "NodeModelAdditive", "NodeModelAttention", "NodeModelHardAttention",
+           "GCNMultiKernel", "GCNLayer", "GCNStack", "GCNModel"]
 _ = L  # keep the binding imported so a missing library fails at import of ops
