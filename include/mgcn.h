@@ -122,6 +122,12 @@ int mgcn_check_device(void *stream, int sync);
  *                   warp-specialised kernel (DWS), 0 = the two-phase kernel
  *   "xw_ws_max"   : 1 (default) = the max adjoint with dX on DWS as well
  *   "xw_ws_full_unroll": DWS gathers in flight per row, 4 / 5 (default) / 6
+ *   "xw_ws_roll"  : how the sum / mean DWS gather waves issue those gathers:
+ *                   0 = in batches (issue all, wait, fold), 2 (default) = a
+ *                   slot takes its next load as soon as it is folded, and the
+ *                   last slots of a row quad take the next quad's first.  Same
+ *                   folds in the same order: same bits.  (The max adjoint
+ *                   always gathers in batches.)
  *   "wide_ws"     : the 256-wide layer kernels: bit 0 the forward, bit 1 the
  *                   adjoint on the warp-specialised form (default 3), else
  *                   the 16-row two-phase form

@@ -199,6 +199,21 @@ __device__ __forceinline__ void meta_rowptr(const int64_t *__restrict__ rowptr, 
   m.deg = ok ? (int32_t)(rowptr[row + 1] - m.beg) : 0;
 }
 
+// meta_rowptr in two parts, for a wave that has gathers in flight when it
+// loads the pointers: the subtraction waits for the pair, so it is left to
+// meta_deg, behind those gathers' folds (until then deg holds the low word of
+// the row's end: a degree fits 32 bits, so the low words' difference is it)
+__device__ __forceinline__ void meta_rowptr_raw(const int64_t *__restrict__ rowptr, int64_t row,
+                                                bool ok, RowMeta &m) {
+  m.beg = ok ? rowptr[row] : 0;
+  // (the low word alone: the pair's unused high word would be a register
+  // that waits for the load before it can be used again)
+  m.deg = ok ? *reinterpret_cast<const int32_t *>(rowptr + row + 1) : 0;
+}
+__device__ __forceinline__ void meta_deg(RowMeta &m) {
+  m.deg = (int32_t)((uint32_t)m.deg - (uint32_t)(uint64_t)m.beg);
+}
+
 __device__ __forceinline__ void meta_first(const int32_t *__restrict__ col,
                                            const float *__restrict__ w, int gl, RowMeta &m) {
   m.mc = 0;
@@ -485,6 +500,154 @@ __device__ __forceinline__ void gather_row2_meta(const __amdgpu_buffer_rsrc_t rx
       }
     }
   }
+}
+
+// Rolling form of gather_row2_meta (sum / mean; "xw_ws_roll" 2): the same
+// slots folded in the same order, but a slot's registers take their next load
+// the moment the slot has been folded, and a quad's last round takes the
+// first slots of the wave's NEXT quad -- so a wave stands with nothing in
+// flight neither between two batches nor under the quad's epilogue (term
+// split, `freed` wait, ring stores, signal).
+template <int U>
+struct RollWin {  // U slots of each of the group's two rows: the rows' 16 B and the edge weights
+  float4 xa[U], xb[U];
+  float wa[U], wb[U];
+};
+
+// register u <- slot k of the rows whose lane-resident (col, w) words are
+// (mca, mwa) / (mcb, mwb); slots at or past na / nb: no access
+template <int U>
+__device__ __forceinline__ void roll_issue(const __amdgpu_buffer_rsrc_t rx, uint32_t ldx_b, int mca,
+                                           int mcb, float mwa, float mwb, int na, int nb, int k,
+                                           int u, int gl, int grp, RollWin<U> &s) {
+  const int ca = bcast_g(mca, grp, k & 31);
+  const int cb = bcast_g(mcb, grp, k & 31);
+  s.wa[u] = bcast_g(mwa, grp, k & 31);
+  s.wb[u] = bcast_g(mwb, grp, k & 31);
+  const uint32_t oa = k < na ? (uint32_t)ca * ldx_b + 16u * gl : 0xfffffff0u;
+  const uint32_t ob = k < nb ? (uint32_t)cb * ldx_b + 16u * gl : 0xfffffff0u;
+  s.xa[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, oa, 0, 0));
+  s.xb[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, ob, 0, 0));
+  // (the loads in slot order, each behind its slot's fold: the folds wait on
+  // counted vmcnt, oldest first)
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// One round: fold the U slots in flight (row a, then row b, ascending) and
+// refill each register at once with slot kn + u of the rows (mc*, mw*).
+// The folds carry no mask: a slot past its row's end was loaded with the "no
+// access" offset and reads +0, its weight is the 1.0 of a lane without an
+// edge, and a sum that started at +0 is never -0, so adding that +0 leaves
+// its bits as they are -- the batch form's skipped slot.
+template <int U>
+__device__ __forceinline__ void roll_round(const __amdgpu_buffer_rsrc_t rx, uint32_t ldx_b, int gl,
+                                           int grp, float (&aa)[4], float (&ab)[4], RollWin<U> &s,
+                                           int mca, int mcb, float mwa, float mwb, int nna,
+                                           int nnb, int kn) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    aa[0] = __fadd_rn(aa[0], __fmul_rn(s.xa[u].x, s.wa[u]));
+    aa[1] = __fadd_rn(aa[1], __fmul_rn(s.xa[u].y, s.wa[u]));
+    aa[2] = __fadd_rn(aa[2], __fmul_rn(s.xa[u].z, s.wa[u]));
+    aa[3] = __fadd_rn(aa[3], __fmul_rn(s.xa[u].w, s.wa[u]));
+    ab[0] = __fadd_rn(ab[0], __fmul_rn(s.xb[u].x, s.wb[u]));
+    ab[1] = __fadd_rn(ab[1], __fmul_rn(s.xb[u].y, s.wb[u]));
+    ab[2] = __fadd_rn(ab[2], __fmul_rn(s.xb[u].z, s.wb[u]));
+    ab[3] = __fadd_rn(ab[3], __fmul_rn(s.xb[u].w, s.wb[u]));
+    // the slot's fold ahead of its refill: left free, the folds sink below
+    // the round's refills, which then need U more slots of registers (spills)
+    asm volatile("" : "+v"(aa[0]), "+v"(aa[1]), "+v"(aa[2]), "+v"(aa[3]), "+v"(ab[0]),
+                      "+v"(ab[1]), "+v"(ab[2]), "+v"(ab[3]));
+    roll_issue<U>(rx, ldx_b, mca, mcb, mwa, mwb, nna, nnb, kn + u, u, gl, grp, s);
+  }
+}
+
+// the first U slots of rows ma / mb (their first 32 (col, w) words lane-resident)
+template <int U>
+__device__ __forceinline__ void roll_first(const __amdgpu_buffer_rsrc_t rx, uint32_t ldx_b,
+                                           const RowMeta &ma, const RowMeta &mb, int gl, int grp,
+                                           RollWin<U> &s) {
+  const int na = ma.deg < 32 ? ma.deg : 32, nb = mb.deg < 32 ? mb.deg : 32;
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    roll_issue<U>(rx, ldx_b, ma.mc, mb.mc, ma.mw, mb.mw, na, nb, u, u, gl, grp, s);
+}
+
+// On entry s holds slots 0 .. U - 1 of rows ma / mb in flight, and on return
+// those of rows xa / xb (the wave's next quad; `carry` false, the last quad:
+// every slot the "no access" offset, nothing is read).  Two empty rows still
+// run one all-masked round, so the carry has one call site.  The rounds that
+// refill from the window and the window's last round are separate code, so
+// the last one's wait for xa / xb's words stands in a straight line behind
+// the loop.  (That wait is counted from the shortest path, a quad of one
+// round: vmcnt(2), most of the round in flight.  Two copies of the last round
+// -- one behind a refill round, with the full count -- cost 75 spilled
+// registers.)  row_a / row_b: the rows (a row longer than one window reads its
+// rowptr again: the rows' beg is not held for it); rsc: the rows' row_scale
+// ('rw'), loaded ahead of the next quad's slots -- loaded behind them, its
+// wait would be theirs too.
+template <int U>
+__device__ __forceinline__ void gather_row2_roll(const __amdgpu_buffer_rsrc_t rx, uint32_t ldx_b,
+                                                 const int64_t *__restrict__ rowptr,
+                                                 const int32_t *__restrict__ col,
+                                                 const float *__restrict__ w, int64_t row_a,
+                                                 int64_t row_b, const RowMeta &ma,
+                                                 const RowMeta &mb, const RowMeta &xa,
+                                                 const RowMeta &xb, bool carry, int gl, int grp,
+                                                 float (&aa)[4], float (&ab)[4], RollWin<U> &s,
+                                                 const float *__restrict__ row_scale,
+                                                 int64_t n_rows, float (&rsc)[2]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) aa[j] = ab[j] = 0.0f;
+  const int32_t da = ma.deg, db = mb.deg;
+  int32_t dm = da > db ? da : db;
+  const int32_t odm = __shfl_xor(dm, 32, 64);
+  // wave-uniform loop bound, in a scalar register: the loops below are then
+  // scalar branches, not exec-masked ones with their copies of the window
+  dm = __builtin_amdgcn_readfirstlane(dm > odm ? dm : odm);
+  if (dm < 1) dm = 1;
+  int mca = ma.mc, mcb = mb.mc;
+  float mwa = ma.mw, mwb = mb.mw;
+  int32_t e0 = 0;
+  do {
+    const int32_t ra = da - e0, rb = db - e0;
+    const int na = ra <= 0 ? 0 : (ra < 32 ? ra : 32);
+    const int nb = rb <= 0 ? 0 : (rb < 32 ? rb : 32);
+    const int32_t remw = dm - e0;
+    const int nbmax = remw < 32 ? remw : 32;  // wave-uniform
+    if (e0 > 0) {  // rows longer than one metadata batch load the rest in place
+      const int32_t my = e0 + gl;
+      mca = mcb = 0;
+      mwa = mwb = 1.0f;
+      if (my < da) {
+        const int64_t beg = rowptr[row_a];
+        mca = col[beg + my];
+        if (w != nullptr) mwa = w[beg + my];
+      }
+      if (my < db) {
+        const int64_t beg = rowptr[row_b];
+        mcb = col[beg + my];
+        if (w != nullptr) mwb = w[beg + my];
+      }
+      // the window's first U slots (the previous window drained at its end).
+      // In this block, behind its loads: the wait for the words is then not
+      // carried, as a maybe, into the rounds, where it would be vmcnt(0).
+#pragma unroll
+      for (int u = 0; u < U; ++u) roll_issue<U>(rx, ldx_b, mca, mcb, mwa, mwb, na, nb, u, u, gl, grp, s);
+    }
+    e0 += 32;
+    for (int k0 = U; k0 < nbmax; k0 += U)  // (slots past a row's end: no access)
+      roll_round<U>(rx, ldx_b, gl, grp, aa, ab, s, mca, mcb, mwa, mwb, na, nb, k0);
+    // the window's last round: the next quad's first slots (nothing at a window boundary)
+    const bool to_next = carry && e0 >= dm;
+    const int nxa = !to_next ? 0 : xa.deg < 32 ? xa.deg : 32;
+    const int nxb = !to_next ? 0 : xb.deg < 32 ? xb.deg : 32;
+    if (row_scale != nullptr && e0 >= dm) {
+      if (row_a < n_rows) rsc[0] = row_scale[row_a];
+      if (row_b < n_rows) rsc[1] = row_scale[row_b];
+    }
+    roll_round<U>(rx, ldx_b, gl, grp, aa, ab, s, xa.mc, xb.mc, xa.mw, xb.mw, nxa, nxb, 0);
+  } while (e0 < dm);
 }
 
 // The row sequence of one lane group in the chunk loop: row k is slot
@@ -1320,10 +1483,11 @@ struct XbsArgs {
   unsigned *err;        // device error word: kDevErrDws when a hand-off gave up
 };
 
-template <int U, int EPI, int MODE>
+template <int U, int EPI, int MODE, int ROLL>
 __global__ __launch_bounds__(kBsThreads) void spmm_xw_bwd_ws_kernel(const XbsArgs A) {
   constexpr bool HCS = MODE == kBsDwsH;  // DWS + dY's column sums (hcs_partial)
   constexpr bool MAXM = MODE == kBsDwsM;  // DWS on the max adjoint (win_mask + slot_map)
+  static_assert(ROLL == 0 || (ROLL == 2 && !MAXM), "the max adjoint keeps the batch gather");
   constexpr bool MRING = MGCN_DS_MASK_RING;
   constexpr int kRing = kDsRingBuf;
   // The max adjoint keeps the timing switches' runtime branches in the
@@ -1391,6 +1555,10 @@ __global__ __launch_bounds__(kBsThreads) void spmm_xw_bwd_ws_kernel(const XbsArg
       meta_rowptr(a.rowptr, row_of(1, j), row_of(1, j) < a.n_rows && wave + kBsNG < n_quads,
                   nxt[j]);
     }
+    // ROLL 2: the quad's first U slots per row are in flight on entry (here:
+    // the first quad's; then issued under the previous quad's last round)
+    RollWin<U> win;
+    if constexpr (ROLL == 2) roll_first<U>(rdy, ldy_b, cur[0], cur[1], gl, grp, win);
     int64_t k = 0;
     for (int64_t q = wave; q < n_quads; q += kBsNG, ++k) {
       RowMeta nn[2];
@@ -1401,7 +1569,10 @@ __global__ __launch_bounds__(kBsThreads) void spmm_xw_bwd_ws_kernel(const XbsArg
         else
           meta_first(a.col, a.w, gl, nxt[j]);
         const int64_t r2 = row_of(k + 2, j);
-        meta_rowptr(a.rowptr, r2, r2 < a.n_rows && q + 2 * kBsNG < n_quads, nn[j]);
+        if constexpr (ROLL == 2)
+          meta_rowptr_raw(a.rowptr, r2, r2 < a.n_rows && q + 2 * kBsNG < n_quads, nn[j]);
+        else
+          meta_rowptr(a.rowptr, r2, r2 < a.n_rows && q + 2 * kBsNG < n_quads, nn[j]);
       }
       const int64_t i = q >> 3;
       const int64_t c = chunk_of(i);
@@ -1441,9 +1612,15 @@ __global__ __launch_bounds__(kBsThreads) void spmm_xw_bwd_ws_kernel(const XbsArg
           yv[j] = __builtin_amdgcn_raw_buffer_load_b128(
               ry, 4 * (int)((lr0 + 2 * j) * a.lddy + 4 * gl), 0, 0);
       }
+      float rsc[2] = {1.0f, 1.0f};  // ROLL 2: row_scale ('rw'), loaded ahead of the next quad's slots
       float acc[2][4];
-      gather_row2_meta<U, MAXM>(rdy, ldy_b, a.col, a.w, cur[0], cur[1], gl, grp, acc[0], acc[1],
-                                a.win_mask, a.slot_map);
+      if constexpr (ROLL == 0)
+        gather_row2_meta<U, MAXM>(rdy, ldy_b, a.col, a.w, cur[0], cur[1], gl, grp, acc[0], acc[1],
+                                  a.win_mask, a.slot_map);
+      else
+        gather_row2_roll<U>(rdy, ldy_b, a.rowptr, a.col, a.w, r0 + lr0, r0 + lr0 + 2, cur[0], cur[1],
+                            nxt[0], nxt[1], q + kBsNG < n_quads, gl, grp, acc[0], acc[1], win,
+                            a.row_scale, a.n_rows, rsc);
       if constexpr (HCS) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -1458,7 +1635,7 @@ __global__ __launch_bounds__(kBsThreads) void spmm_xw_bwd_ws_kernel(const XbsArg
       for (int j = 0; j < 2; ++j) {
         const int64_t row = r0 + lr0 + 2 * j;
         if (a.row_scale != nullptr && row < a.n_rows) {
-          const float sc = a.row_scale[row];
+          const float sc = ROLL == 2 ? rsc[j] : a.row_scale[row];
 #pragma unroll
           for (int t = 0; t < 4; ++t) acc[j][t] = __fmul_rn(acc[j][t], sc);
         }
@@ -1484,6 +1661,7 @@ __global__ __launch_bounds__(kBsThreads) void spmm_xw_bwd_ws_kernel(const XbsArg
       for (int j = 0; j < 2; ++j) {
         cur[j] = nxt[j];
         nxt[j] = nn[j];
+        if constexpr (ROLL == 2) meta_deg(nxt[j]);
       }
     }
   } else {
@@ -1701,18 +1879,34 @@ int bs_grid() {
   return cus;  // one workgroup per CU
 }
 
+template <int U, int MODE, int ROLL>
+int launch_bs_ur(const XbsArgs &a, int epi, int grid, hipStream_t s) {
+  if (epi == EPI_RELU_DIV)
+    hipLaunchKernelGGL((spmm_xw_bwd_ws_kernel<U, EPI_RELU_DIV, MODE, ROLL>), dim3(grid),
+                       dim3(kBsThreads), 0, s, a);
+  else if (epi == EPI_RELU)
+    hipLaunchKernelGGL((spmm_xw_bwd_ws_kernel<U, EPI_RELU, MODE, ROLL>), dim3(grid),
+                       dim3(kBsThreads), 0, s, a);
+  else
+    hipLaunchKernelGGL((spmm_xw_bwd_ws_kernel<U, EPI_STORE, MODE, ROLL>), dim3(grid),
+                       dim3(kBsThreads), 0, s, a);
+  return check_launch("spmm_xw_bwd_ws_kernel");
+}
+
+// mgcn_set_option("xw_ws_roll"): the sum / mean DWS gather waves' load
+// schedule -- 0 batches, 2 a slot refilled as it is folded, within a quad and
+// into the next (config 2: 4.72-4.73 vs 4.82-4.84 ms/step; 1, the refill
+// within a quad alone, gained a third of that and is removed: DESIGN section 4)
+int g_bs_roll = 2;
+
 template <int U, int MODE>
 int launch_bs_u(const XbsArgs &a, int epi, int grid, hipStream_t s) {
-  if (epi == EPI_RELU_DIV)
-    hipLaunchKernelGGL((spmm_xw_bwd_ws_kernel<U, EPI_RELU_DIV, MODE>), dim3(grid), dim3(kBsThreads),
-                       0, s, a);
-  else if (epi == EPI_RELU)
-    hipLaunchKernelGGL((spmm_xw_bwd_ws_kernel<U, EPI_RELU, MODE>), dim3(grid), dim3(kBsThreads), 0,
-                       s, a);
-  else
-    hipLaunchKernelGGL((spmm_xw_bwd_ws_kernel<U, EPI_STORE, MODE>), dim3(grid), dim3(kBsThreads), 0,
-                       s, a);
-  return check_launch("spmm_xw_bwd_ws_kernel");
+  if constexpr (MODE == kBsDwsM) {
+    return launch_bs_ur<U, MODE, 0>(a, epi, grid, s);
+  } else {
+    return g_bs_roll == 0 ? launch_bs_ur<U, MODE, 0>(a, epi, grid, s)
+                          : launch_bs_ur<U, MODE, 2>(a, epi, grid, s);
+  }
 }
 
 // mgcn_set_option("xw_ws_dbg") (experiment builds): timing experiments (dW / dX
@@ -1771,6 +1965,7 @@ int xw_set_ws(const char *name, int value) {
                                : unroll(g_xw_pk_bwd_unroll, {2, 3, 4});
   }
   if (n == "xw_ws_max") return flag(g_xw_ws_max);
+  if (n == "xw_ws_roll") return unroll(g_bs_roll, {0, 2});
   if (n == "xw_ws_full") return flag(g_xw_ws_full);
   if (n == "xw_ws_dbg") {  // (timing experiments: results WRONG when set)
     if (!MGCN_EXPERIMENT) {
