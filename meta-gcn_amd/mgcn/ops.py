@@ -16,6 +16,7 @@ max routes through the saved argmax), so the adjoint is bit-identical too.
 """
 from __future__ import annotations
 
+import enum
 import os
 from collections import Counter
 from dataclasses import dataclass
@@ -35,28 +36,12 @@ _TIMER = None
 _FUSE_XW = os.environ.get("MGCN_FUSE_XW", "1") != "0"
 
 
-# Middle layers of a stack (dX wanted, a ReLU mask below) keep the dW + dX
-# gather kernel: Z write + dW pass + dX-only gather cost 1.18 ms there
-# against 1.15 for the one kernel; the top layer (its bias gradient rides in
-# the dW pass) and the bottom layer (no gather at all) take the Z form.
-# MGCN_Z_MIDDLE=1 sends the middle layers through Z as well.
+# The route switches of a GCN stack: :func:`_plan_stack` reads them, once per
+# forward, and says what each one selects.
 _Z_MIDDLE = os.environ.get("MGCN_Z_MIDDLE", "0") != "0"
-# the top 128-wide layer of a stack (sum, no ReLU) takes the dW + dX adjoint
-# (the DWS kernel) instead of keeping Z for the dense Z^T dY pass: env
-# MGCN_TOP_FULL=0 turns it off.  Its bias gradient (dY's column sums) comes
-# from a column-sum pass over dY (0.095 ms) -- config 2: 5.02 vs 5.04-5.07
-# ms/step (A/B on one box) -- or, MGCN_TOP_HCS=1, from the adjoint launch
-# itself (mgcn_spmm_xw_bwd_hcs: its dY row reads and their registers cost
-# that launch ~0.25 ms, 5.16-5.19)
 _TOP_FULL = os.environ.get("MGCN_TOP_FULL", "1") != "0"
 _TOP_HCS = os.environ.get("MGCN_TOP_HCS", "0") != "0"
-# (with _TOP_FULL: the top bias gradient from the bottom layer's dW pass, which
-# streams dY beside its own operands -- mgcn_gemm_bwd_dw_cs; env
-# MGCN_TOP_CS_DEFER=0: a column-sum pass of its own)
 _TOP_CS_DEFER = os.environ.get("MGCN_TOP_CS_DEFER", "1") != "0"
-# max layers with dX: the dW + dX adjoint with the winner-bit routing in one
-# launch (mgcn_spmm_xw_bwd with win_mask: the warp-specialised kernel) instead
-# of mgcn_spmm_bwd + mgcn_gemm_bwd: env MGCN_MAX_FULL=0 turns it off
 _MAX_FULL = os.environ.get("MGCN_MAX_FULL", "1") != "0"
 
 
@@ -1136,74 +1121,198 @@ def gcn_layer(x: torch.Tensor, W: torch.Tensor, plan: GraphPlan, norm: NormPlan,
     return aggregate_plan(linear(x, W), plan, norm, aggr, bias, relu)
 
 
+class _Bwd(enum.Enum):
+    """The backward route of one layer of a GCN stack (:func:`_plan_stack`)."""
+    NONE = "none"                # frozen weight at the bottom, x without gradient
+    DX_ONLY = "dx_only"          # frozen weight: the dX-only adjoint
+    Z_FORM = "z_form"            # dense dW = Z^T dY pass + the dX-only adjoint
+    FULL = "full"                # the one-pass dW + dX adjoint
+    FULL_DW = "full_dw"          # its dW-only form (bottom layer, x without gradient)
+    GEMM_BWD = "gemm_bwd"        # spmm_bwd, then dW + dX from one gemm_bwd
+    GEMM_BWD_DW = "gemm_bwd_dw"  # spmm_bwd, then gemm_bwd's dW-only form
+    GENERIC = "generic"          # spmm_bwd, then gemm_tn and a dX product
+
+
+class _TopBias(enum.Enum):
+    """Where a GCN stack's top-layer bias gradient (dZ's column sums) comes from."""
+    COLSUM_PASS = "colsum_pass"      # relu_bwd_colsum over dZ (also the top ReLU / mean)
+    TOP_DW_PASS = "top_dw_pass"      # the top layer's own Z^T dY pass
+    ADJOINT = "adjoint"              # the top layer's dW + dX adjoint launch
+    BOTTOM_DW_PASS = "bottom_dw_pass"  # the bottom layer's Z^T dY pass (dw_pass_cs)
+
+
+@dataclass(frozen=True)
+class _LayerPlan:
+    fused_fwd: bool    # spmm_xw_fwd; otherwise the GEMM, then spmm_fwd
+    write_mask: bool   # the forward writes the ReLU mask the layer above reads
+    keep_z: bool       # the forward keeps the aggregate Z = A h (bwd is Z_FORM)
+    winner_bits: bool  # max on spmm_fwd: the adjoint routes dY through the winners
+    bwd: _Bwd
+    epilogue: bool     # the lower layer's ReLU / bias gradient / mean divisor ride in this dX
+    want_dw: bool
+    want_dx: bool      # every layer but the bottom one; there: x needs a gradient
+
+
+@dataclass(frozen=True)
+class _StackPlan:
+    layers: tuple
+    top_bias: _TopBias
+
+
+def _plan_stack(shapes, relus, has_bias, need_w, need_x: bool, reduce: int, fwd: CSRView,
+                bwd: CSRView, ld_x: int) -> _StackPlan:
+    """Every launch decision of a :class:`_GCNStack`, taken once, before its
+    forward: ``shapes`` the layers' (F_in, F_out), ``need_w`` which weights
+    want a gradient, ``ld_x`` the leading dimension of the stack's input.  Of
+    the views only n_rows, n_cols and n_heavy are read, no tensor data: the
+    plan is a function of these arguments, the module switches and libmgcn's
+    ``*_supported`` probes.
+
+    Forward.  A layer the fused kernel takes (128 -> 128 or 256 -> 256, sum /
+    mean, no heavy rows: :func:`spmm_xw_supported`; ``MGCN_FUSE_XW=0`` turns
+    every fused kernel off) aggregates then multiplies in one launch, (A h) W,
+    and h W is never written; any other runs the GEMM, then the SpMM (max does
+    not commute with W), which for max leaves each edge's winner bits.  A ReLU
+    layer writes its mask (16 B per row and 128 features) iff the layer above
+    reads it in its dX epilogue: mgcn_gemm_nn's fused ReLU backward (N <= 128)
+    or, for the 8-word masks that only a 256-wide fused forward writes, the
+    dX-only adjoint.
+
+    Backward, top layer first; each layer takes the first route that applies.
+      * NONE / DX_ONLY: a frozen weight wants no dW -- nothing at the bottom of
+        a stack whose x wants no gradient, otherwise the dX-only adjoint where
+        it applies (no max; the lower layer's mask kept, or the bottom layer).
+        A frozen weight it does not take falls through to the routes below
+        and its dW is dropped.
+      * Z_FORM: the forward kept Z = A h (mean: the undivided sum, dY arrives
+        divided by the counts), dW = Z^T dY is one dense pass and the gather
+        runs only for dX, so the bottom layer runs no gather at all.  For the
+        bottom layer, or one above a kept mask, whose weight wants a gradient
+        and whose adjoint the fused kernel takes; but not for a middle layer
+        (Z write + dW pass + dX-only gather cost 1.18 ms there against 1.15
+        for the one kernel; ``MGCN_Z_MIDDLE=1`` sends them through Z too) nor,
+        by default, for a 128-wide top layer without ReLU on a square graph:
+        with the adjoint at 0.99 ms it is cheaper on FULL than Z's write, the
+        dX-only adjoint and the dense pass (``MGCN_TOP_FULL=0``: Z_FORM).
+        256-wide layers have no FULL form and always take Z.
+      * FULL: adjoint SpMM, dW and dX with the lower layer's epilogue in one
+        pass, dH never leaves the chip; 128 x 128 above a kept mask.  Max
+        routes dY through the forward's winner bits in the same launch (the
+        warp-specialised kernel; ``MGCN_MAX_FULL=0``: spmm_bwd + gemm_bwd).
+        FULL_DW is its dW-only form at a bottom layer whose x wants no gradient.
+      * GEMM_BWD / GEMM_BWD_DW / GENERIC: spmm_bwd writes dH; then one
+        gemm_bwd for dW and dX (128 x 128 above a kept mask), its dW-only form
+        (bottom, x without gradient), or gemm_tn for dW and, for dX,
+        gemm_nn with the mask epilogue / a plain product and relu_bwd_colsum.
+
+    The top layer's bias gradient is the column sums of dZ.  Without a top
+    ReLU or mean they come free from the top layer's own Z^T dY pass
+    (TOP_DW_PASS); with the top layer on FULL from the bottom layer's Z^T dY
+    pass, which streams dZ beside its own operands (BOTTOM_DW_PASS,
+    mgcn_gemm_bwd_dw_cs: 0.245 vs 0.224 ms for the plain pass, config 2
+    4.89-4.90 vs 4.95-4.96 ms/step; ``MGCN_TOP_CS_DEFER=0`` turns it off) or,
+    ``MGCN_TOP_HCS=1``, from the FULL launch itself (ADJOINT,
+    mgcn_spmm_xw_bwd_hcs: its dY row reads and their registers cost that
+    launch ~0.25 ms, 5.16-5.19).  Otherwise a relu_bwd_colsum pass over dZ
+    (COLSUM_PASS, 0.095 ms), which also applies the top ReLU and mean's
+    division."""
+    fuse, z_middle, top_full, top_hcs, cs_defer, max_full = (
+        _FUSE_XW, _Z_MIDDLE, _TOP_FULL, _TOP_HCS, _TOP_CS_DEFER, _MAX_FULL)
+    top = len(shapes) - 1
+    mean = reduce == L.REDUCE_MEAN
+    square = bwd.n_rows == bwd.n_cols
+
+    def adjoint_ok(l):  # the fused adjoint gathers layer l's dY over the bwd view
+        return spmm_xw_supported(bwd, shapes[l][1], shapes[l][0], L.REDUCE_SUM)
+
+    layers = []
+    for l, (f_in, f_out) in enumerate(shapes):
+        xw = bool(fuse and spmm_xw_supported(fwd, f_in, f_out, reduce, ld_x if l == 0 else None))
+        mask = bool(relus[l] and l < top and (
+            gemm_nn_epi_supported(shapes[l + 1][1], shapes[l + 1][0]) or
+            (xw and f_out > 128 and adjoint_ok(l + 1))))
+        epilogue = l > 0 and layers[l - 1].write_mask
+        winners = reduce == L.REDUCE_MAX and not xw
+        want_dw, want_dx = bool(need_w[l]), l > 0 or bool(need_x)
+        full_ok = fuse and xw_full_supported(f_in, f_out) and adjoint_ok(l)
+        middle = 0 < l < top and relus[l - 1]
+        on_full = (top_full and l == top and epilogue and not relus[l] and
+                   reduce in (L.REDUCE_SUM, L.REDUCE_MEAN) and square and
+                   xw_full_supported(f_in, f_out))
+        keep_z = bool(xw and want_dw and (l == 0 or epilogue) and not on_full and
+                      (z_middle or not middle or not xw_full_supported(f_in, f_out)) and
+                      dw_pass_supported(f_in, f_out) and adjoint_ok(l))
+        if not want_dw and not want_dx:
+            route = _Bwd.NONE
+        elif not want_dw and not winners and (l == 0 or epilogue) and fuse and adjoint_ok(l):
+            route = _Bwd.DX_ONLY
+        elif keep_z:
+            route = _Bwd.Z_FORM
+        elif full_ok and epilogue and (not winners or max_full):
+            route = _Bwd.FULL
+        elif full_ok and not want_dx:
+            route = _Bwd.FULL_DW
+        elif epilogue and gemm_bwd_supported(f_in, f_out):
+            route = _Bwd.GEMM_BWD
+        elif not want_dx and gemm_bwd_supported(f_in, f_out):
+            route = _Bwd.GEMM_BWD_DW
+        else:
+            route = _Bwd.GENERIC
+        layers.append(_LayerPlan(xw, mask, keep_z, winners, route, epilogue, want_dw, want_dx))
+
+    plain_top = not relus[top] and not mean  # dY = dZ as it is
+    if plain_top and layers[top].keep_z:
+        top_bias = _TopBias.TOP_DW_PASS
+    elif (plain_top and top_full and top_hcs and layers[top].bwd is _Bwd.FULL and
+          not layers[top].winner_bits and has_bias[top] and square):
+        top_bias = _TopBias.ADJOINT
+    elif (plain_top and cs_defer and top > 0 and has_bias[top] and layers[0].keep_z and
+          gemm_bwd_supported(*shapes[0]) and shapes[top][1] == 128):
+        top_bias = _TopBias.BOTTOM_DW_PASS
+    else:
+        top_bias = _TopBias.COLSUM_PASS
+    return _StackPlan(tuple(layers), top_bias)
+
+
 class _GCNStack(torch.autograd.Function):
     """A chain of GCN layers  Z_l = act_l(A_norm (Z_{l-1} W_l) + b_l)  as one
-    autograd node, so the backward can fuse across layer boundaries: the
-    ReLU mask and bias gradient of layer l-1 are computed in the epilogue of
-    layer l's dX GEMM (mgcn_gemm_nn with Z), instead of a separate pass.
-    Per layer: GEMM -> SpMM(+bias, ReLU) forward; SpMM^T, dW (split-K), dX
-    (+ fused ReLU/bias of the layer below) backward.  Same math and the same
-    per-edge summation order as the layer-by-layer modules.
-    128 -> 128 sum / mean layers run fused: the forward aggregates then
-    multiplies ((A h) W, one launch) and keeps Z = A h; the backward forms
-    dW = Z^T dY in one dense pass (the top layer's bias gradient from the
-    same pass) and gathers A^T dY only for dX, so the bottom layer runs no
-    gather.  Max keeps the GEMM + SpMM launches (max does not commute with W)."""
+    autograd node, so the backward can fuse across layer boundaries: the ReLU
+    mask and bias gradient of layer l-1 are computed in the epilogue of layer
+    l's dX, instead of a separate pass.  :func:`_plan_stack` chooses every
+    launch of both directions before the forward runs; the forward executes
+    its half and leaves the plan on ``ctx`` for the backward.  Same math and
+    the same per-edge summation order as the layer-by-layer modules."""
 
     @staticmethod
     def forward(ctx, x, plan, norm, reduce, relus, *params):
         Ws, bs = params[0::2], params[1::2]
+        n = len(Ws)
+        has_bias = [b is not None for b in bs]
+        route = _plan_stack([tuple(W.shape) for W in Ws], relus, has_bias,
+                            [ctx.needs_input_grad[5 + 2 * i] for i in range(n)],
+                            ctx.needs_input_grad[0], reduce, plan.fwd, plan.bwd, x.stride(0))
         h = x
         inputs, outs, args, rmasks, zs = [], [], [], [], []
-        for i, (W, b, relu) in enumerate(zip(Ws, bs, relus)):
-            z = None
+        for W, b, relu, lp in zip(Ws, bs, relus, route.layers):
             inputs.append(h)
-            # the ReLU mask the next layer's dX GEMM reads (16 B per row)
-            nxt = Ws[i + 1] if i + 1 < len(Ws) else None
-            rm = None
-            xw = _FUSE_XW and spmm_xw_supported(plan.fwd, W.size(0), W.size(1), reduce,
-                                                h.stride(0))
-            if relu and nxt is not None and (
-                    gemm_nn_epi_supported(nxt.size(1), nxt.size(0)) or
-                    (xw and W.size(1) > 128 and
-                     spmm_xw_supported(plan.bwd, nxt.size(1), nxt.size(0), L.REDUCE_SUM))):
-                # (the 8-word masks of a 256-wide layer only from its fused
-                # forward, for the fused dX-only adjoint of the next layer)
+            z = am = rm = None
+            if lp.write_mask:
                 rm = torch.empty(plan.fwd.n_rows, mask_words(W.size(1)), dtype=torch.int32,
                                  device=h.device)
-            if xw:
-                # (A h) W in one launch: h @ W is never written (sum / mean);
-                # the aggregate A h is kept for dW = (A h)^T dY when the
-                # backward takes that form (same predicate as its z_path):
-                # the bottom layer, or one whose lower layer left a ReLU
-                # mask, with the dX-only gather possible on the bwd view;
-                # middle layers keep the dW + dX gather kernel (_Z_MIDDLE)
-                below = i == 0 or (relus[i - 1] and rmasks[i - 1] is not None)
-                middle = 0 < i < len(Ws) - 1 and relus[i - 1]
-                top_full = (_TOP_FULL and i == len(Ws) - 1 and i > 0 and relus[i - 1] and
-                            rmasks[i - 1] is not None and not relu and
-                            reduce in (L.REDUCE_SUM, L.REDUCE_MEAN) and
-                            plan.bwd.n_rows == plan.bwd.n_cols and xw_full_supported(*W.shape))
-                want_z = (bool(ctx.needs_input_grad[5 + 2 * i]) and below and not top_full and
-                          (_Z_MIDDLE or not middle or
-                           not xw_full_supported(*W.shape)) and
-                          dw_pass_supported(W.size(0), W.size(1)) and
-                          spmm_xw_supported(plan.bwd, W.size(1), W.size(0), L.REDUCE_SUM))
-                h, am = spmm_xw_fwd(plan.fwd, norm.w_fwd, h, W, reduce, b, relu,
-                                    relu_mask=rm, want_z=want_z), None
-                if want_z:
+            if lp.fused_fwd:
+                h = spmm_xw_fwd(plan.fwd, norm.w_fwd, h, W, reduce, b, relu, relu_mask=rm,
+                                want_z=lp.keep_z)
+                if lp.keep_z:
                     h, z = h
             else:
-                H = _mm(h, W)
-                h, am = spmm_fwd(plan.fwd, norm.w_fwd, H, reduce, b, relu, mask_plan=plan,
+                h, am = spmm_fwd(plan.fwd, norm.w_fwd, _mm(h, W), reduce, b, relu, mask_plan=plan,
                                  relu_mask=rm)
             outs.append(h)
             args.append(am)  # max: winner bits per edge (adjoint slot order)
             rmasks.append(rm)
             zs.append(z)
         ctx.plan, ctx.norm, ctx.reduce, ctx.relus = plan, norm, reduce, relus
-        ctx.n_layers = len(Ws)
-        ctx.has_bias = [b is not None for b in bs]
+        ctx.n_layers, ctx.has_bias, ctx.route = n, has_bias, route
         ctx.save_for_backward(*inputs, *outs, *[a if a is not None else torch.empty(0)
                                                 for a in args], *Ws,
                               *[m if m is not None else torch.empty(0) for m in rmasks],
@@ -1218,148 +1327,92 @@ class _GCNStack(torch.autograd.Function):
         args, Ws, rmasks = saved[2 * n:3 * n], saved[3 * n:4 * n], saved[4 * n:5 * n]
         zs = saved[5 * n:6 * n]
         plan, norm, reduce, relus = ctx.plan, ctx.norm, ctx.reduce, ctx.relus
+        has_bias, top_bias = ctx.has_bias, ctx.route.top_bias
+        view, w_t, scale = plan.bwd, norm.w_bwd, norm.row_scale_bwd
         gW = [None] * n
         gb = [None] * n
         top = n - 1
         # mean: every layer's dY is produced divided by the row counts (fused
-        # into relu_bwd_colsum / the dX GEMM epilogue); the adjoint is a sum
+        # into relu_bwd_colsum / the dX epilogue); the adjoint is a sum
         mean = reduce == L.REDUCE_MEAN
         rd = plan.in_cnt if mean else None
         adj = L.REDUCE_SUM if mean else reduce
-
-        def z_path(l):  # dW = Z^T dY from the forward's aggregate (below)
-            fused = l > 0 and relus[l - 1] and rmasks[l - 1].numel() > 0
-            return bool(zs[l].numel() and (fused or l == 0) and
-                        dw_pass_supported(Ws[l].size(0), Ws[l].size(1)) and
-                        spmm_xw_supported(plan.bwd, Ws[l].size(1), Ws[l].size(0),
-                                          L.REDUCE_SUM))
-
-        top_z = z_path(top) and not relus[top] and rd is None
-        # the top layer's bias gradient from its dW + dX adjoint (mgcn_spmm_xw_bwd_hcs):
-        # the forward kept no Z for it (top_full there); same predicate here
-        top_hcs = (_TOP_FULL and _TOP_HCS and not zs[top].numel() and top > 0 and not relus[top] and
-                   rd is None and args[top].numel() == 0 and relus[top - 1] and
-                   rmasks[top - 1].numel() > 0 and ctx.needs_input_grad[5 + 2 * top] and
-                   ctx.has_bias[top] and plan.bwd.n_rows == plan.bwd.n_cols and
-                   _FUSE_XW and xw_full_supported(*Ws[top].shape) and
-                   spmm_xw_supported(plan.bwd, Ws[top].size(0), Ws[top].size(1), L.REDUCE_SUM))
-        # or from the bottom layer's dW = Z^T dY pass, which streams dZ beside
-        # its own operands (mgcn_gemm_bwd_dw_cs): no separate pass over dZ
-        top_defer = (not top_z and not top_hcs and _TOP_CS_DEFER and top > 0 and
-                     not relus[top] and rd is None and ctx.has_bias[top] and
-                     ctx.needs_input_grad[5] and z_path(0) and
-                     gemm_bwd_supported(*Ws[0].shape) and tuple(dZ.shape) == (zs[0].size(0), 128))
-        top_S = None
-        if top_z or top_hcs or top_defer:
-            # dY = dZ as it is: its column sums (the top bias gradient) come
-            # from the dW = Z^T dY pass below, from the top layer's dW + dX
-            # adjoint (top_hcs) or from the bottom layer's dW pass (top_defer),
-            # no separate read of dZ
-            dY = dZ.contiguous()
-            if top_defer:
-                top_S = dY
+        dZ = dZ.contiguous()
+        if top_bias is _TopBias.COLSUM_PASS:
+            dY, gb[top] = relu_bwd_colsum(dZ, outs[top], relus[top], has_bias[top], row_div=rd)
         else:
-            dY, db = relu_bwd_colsum(dZ.contiguous(), outs[top], relus[top], ctx.has_bias[top],
-                                     row_div=rd)
-            gb[top] = db
-        dx = None
+            dY = dZ  # its column sums come from a later launch, no separate read of dZ
 
-        def adjoint_dx(l, dY):
-            """Layer l's dX-only adjoint -> the lower layer's dY (with its ReLU
-            mask, bias gradient and mean divisor)."""
-            W = Ws[l]
-            _, dYn, db = spmm_xw_bwd(plan.bwd, norm.w_bwd, norm.row_scale_bwd, dY, None, W,
-                                     relu_mask=rmasks[l - 1], row_div=rd)
-            gb[l - 1] = db if ctx.has_bias[l - 1] else None
-            return dYn
+        def lower_bias(l, db):
+            gb[l - 1] = db if has_bias[l - 1] else None
 
+        def gather_dx(l, dY, lp):
+            """Layer l's dX-only adjoint: the lower layer's dY (through its ReLU
+            mask and mean divisor, with its bias gradient), or the stack's dx."""
+            if lp.epilogue:
+                _, dY, db = spmm_xw_bwd(view, w_t, scale, dY, None, Ws[l], relu_mask=rmasks[l - 1],
+                                        row_div=rd)
+                lower_bias(l, db)
+                return dY
+            if lp.want_dx:
+                return spmm_xw_bwd(view, w_t, scale, dY, None, Ws[l])[1]
+            return None
+
+        # dY: the gradient of layer l's output on entry, of its input on exit
         for l in range(top, -1, -1):
-            am = args[l] if args[l].numel() else None
-            W = Ws[l]
-            fused = l > 0 and relus[l - 1] and rmasks[l - 1].numel() > 0
-            if not ctx.needs_input_grad[5 + 2 * l]:
-                # a frozen weight: no dW; only dX (with the lower layer's ReLU
-                # / bias gradient) is wanted -- the dX-only adjoint, which
-                # also takes the 8-word masks of a 256-wide layer
-                if l == 0 and not ctx.needs_input_grad[0]:
-                    continue
-                if am is None and (fused or l == 0) and _FUSE_XW and \
-                        spmm_xw_supported(plan.bwd, W.size(1), W.size(0), L.REDUCE_SUM):
-                    if fused:
-                        dY = adjoint_dx(l, dY)
-                    else:
-                        dx = spmm_xw_bwd(plan.bwd, norm.w_bwd, norm.row_scale_bwd, dY, None, W)[1]
-                    continue
-            if z_path(l):
-                # dW = Z^T dY from the forward's aggregate Z = A h (a dense
-                # pass over Z and dY, no gather); mean: Z is the undivided sum
-                # and dY arrives divided by the counts, so Z^T dY is the same
-                # product.  The gather runs only for dX (+ the lower layer's
-                # ReLU / bias gradient); the bottom layer needs no gather at all.
-                hcs = bool(top_z and l == top and ctx.has_bias[top])
-                if gW[l] is None and top_S is not None and l == 0:
-                    gW[l], gb[top] = dw_pass_cs(zs[l], dY, top_S)  # + the top bias gradient
-                elif gW[l] is None:
+            lp, W = ctx.route.layers[l], Ws[l]
+            if lp.bwd is _Bwd.NONE:
+                dY = None
+                continue
+            am = args[l] if lp.winner_bits else None
+            sm = plan.slot_map() if lp.winner_bits else None
+            if lp.bwd is _Bwd.DX_ONLY:
+                dY = gather_dx(l, dY, lp)
+            elif lp.bwd is _Bwd.Z_FORM:
+                if l == 0 and top_bias is _TopBias.BOTTOM_DW_PASS:
+                    gW[l], gb[top] = dw_pass_cs(zs[l], dY, dZ)
+                else:
+                    hcs = l == top and top_bias is _TopBias.TOP_DW_PASS and has_bias[top]
                     gW[l], cs = dw_pass(zs[l], dY, W, dh_colsum=hcs)
                     if hcs:
                         gb[top] = cs
-                if fused:
-                    dY = adjoint_dx(l, dY)
-                elif ctx.needs_input_grad[0]:
-                    dx = spmm_xw_bwd(plan.bwd, norm.w_bwd, norm.row_scale_bwd, dY, None, W)[1]
-                continue
-            if (_FUSE_XW and xw_full_supported(W.size(0), W.size(1)) and
-                    spmm_xw_supported(plan.bwd, W.size(0), W.size(1), L.REDUCE_SUM)):
-                # adjoint SpMM + dW + dX (+ the lower layer's ReLU / bias
-                # gradient) in one pass: dH never leaves the chip (max: the
-                # adjoint routes dY through the forward's winner bits; with dX
-                # the two-phase kernel measured slower than the two launches,
-                # 1.53 vs 1.42 ms at config 4; the warp-specialised one is
-                # faster, _MAX_FULL)
-                sm = plan.slot_map() if am is not None else None
-                if fused and (am is None or _MAX_FULL):
-                    hcs = None
-                    if top_hcs and l == top:
-                        hcs = gb[top] = torch.empty(W.size(1), dtype=torch.float32,
-                                                    device=dY.device)
-                    gW[l], dY, db = spmm_xw_bwd(plan.bwd, norm.w_bwd, norm.row_scale_bwd, dY,
-                                                inputs[l], W, relu_mask=rmasks[l - 1],
-                                                row_div=rd, win_mask=am, slot_map=sm,
-                                                dy_colsum_out=hcs)
-                    gb[l - 1] = db if ctx.has_bias[l - 1] else None
-                    continue
-                if l == 0 and not ctx.needs_input_grad[0]:
-                    gW[l] = spmm_xw_bwd(plan.bwd, norm.w_bwd, norm.row_scale_bwd, dY, inputs[l],
-                                        W, want_dx=False, win_mask=am, slot_map=sm)[0]
-                    continue
-            dH = spmm_bwd(plan.bwd, norm.w_bwd, norm.row_scale_bwd, dY, adj, win_mask=am,
-                          slot_map=plan.slot_map() if am is not None else None)
-            if fused and gemm_bwd_supported(W.size(0), W.size(1)):
-                # dW and dX (+ the lower layer's ReLU / bias gradient) in one pass
-                gW[l], dY, db = gemm_bwd(inputs[l], dH, W, relu_mask=rmasks[l - 1], row_div=rd)
-                gb[l - 1] = db if ctx.has_bias[l - 1] else None
-                continue
-            if l == 0 and not ctx.needs_input_grad[0] and gemm_bwd_supported(W.size(0), W.size(1)):
-                gW[l] = gemm_bwd(inputs[l], dH, W, want_dx=False)[0]  # dW alone, same pass shape
-                continue
-            if ctx.needs_input_grad[5 + 2 * l]:
-                gW[l] = gemm_tn(inputs[l], dH)
-            if l > 0:
-                if fused:
-                    dY, db = gemm_nn(dH, W, transpose_w=True, relu_mask=rmasks[l - 1],
-                                     row_div=rd)
-                    if not ctx.has_bias[l - 1]:
-                        db = None
+                dY = gather_dx(l, dY, lp)
+            elif lp.bwd is _Bwd.FULL:
+                hcs = None
+                if l == top and top_bias is _TopBias.ADJOINT:
+                    hcs = gb[top] = torch.empty(W.size(1), dtype=torch.float32, device=dY.device)
+                gW[l], dY, db = spmm_xw_bwd(view, w_t, scale, dY, inputs[l], W,
+                                            relu_mask=rmasks[l - 1], row_div=rd, win_mask=am,
+                                            slot_map=sm, dy_colsum_out=hcs)
+                lower_bias(l, db)
+            elif lp.bwd is _Bwd.FULL_DW:
+                gW[l] = spmm_xw_bwd(view, w_t, scale, dY, inputs[l], W, want_dx=False,
+                                    win_mask=am, slot_map=sm)[0]
+                dY = None
+            else:
+                dH = spmm_bwd(view, w_t, scale, dY, adj, win_mask=am, slot_map=sm)
+                dY = None
+                if lp.bwd is _Bwd.GEMM_BWD:
+                    gW[l], dY, db = gemm_bwd(inputs[l], dH, W, relu_mask=rmasks[l - 1], row_div=rd)
+                    lower_bias(l, db)
+                elif lp.bwd is _Bwd.GEMM_BWD_DW:
+                    gW[l] = gemm_bwd(inputs[l], dH, W, want_dx=False)[0]
                 else:
-                    dY, db = relu_bwd_colsum(_mm_t(dH, W), outs[l - 1], relus[l - 1],
-                                             ctx.has_bias[l - 1], row_div=rd)
-                gb[l - 1] = db
-            elif ctx.needs_input_grad[0]:
-                dx = _mm_t(dH, W)
+                    if lp.want_dw:
+                        gW[l] = gemm_tn(inputs[l], dH)
+                    if lp.epilogue:
+                        dY, db = gemm_nn(dH, W, transpose_w=True, relu_mask=rmasks[l - 1],
+                                         row_div=rd)
+                        lower_bias(l, db)
+                    elif l > 0:
+                        dY, gb[l - 1] = relu_bwd_colsum(_mm_t(dH, W), outs[l - 1], relus[l - 1],
+                                                        has_bias[l - 1], row_div=rd)
+                    elif lp.want_dx:
+                        dY = _mm_t(dH, W)
         grads = []
         for w, b in zip(gW, gb):
             grads += [w, b]
-        return (dx, None, None, None, None, *grads)
+        return (dY, None, None, None, None, *grads)
 
 
 def gcn_stack(x: torch.Tensor, plan: GraphPlan, norm: NormPlan, Ws, bs, relus,
