@@ -378,10 +378,8 @@ extern "C" int mgcn_relu_bwd_colsum(int64_t n_rows, int32_t F, const float *dZ, 
   float *partial = nullptr;
   if (db != nullptr) {
     const size_t need = mgcn_colsum_workspace_bytes(n_rows, F);
-    if (workspace == nullptr || workspace_bytes < need) {
-      set_error("mgcn_relu_bwd_colsum: workspace %zu < %zu", workspace_bytes, need);
-      return MGCN_EWORKSPACE;
-    }
+    if (int rc = require_workspace("mgcn_relu_bwd_colsum", workspace, workspace_bytes, need))
+      return rc;
     partial = static_cast<float *>(workspace);
   }
   const bool v4 = (F % 4 == 0) && ((uintptr_t)dZ % 16 == 0) && (!relu || (uintptr_t)Z % 16 == 0) &&
@@ -538,10 +536,8 @@ extern "C" int mgcn_residual_act_bwd(int64_t n_rows, int32_t F, const float *dZ,
   float *partial = nullptr;
   if (colsums != nullptr) {
     const size_t need = mgcn_residual_act_bwd_workspace_bytes(n_rows, F);
-    if (workspace == nullptr || workspace_bytes < need) {
-      set_error("mgcn_residual_act_bwd: workspace %zu < %zu", workspace_bytes, need);
-      return MGCN_EWORKSPACE;
-    }
+    if (int rc = require_workspace("mgcn_residual_act_bwd", workspace, workspace_bytes, need))
+      return rc;
     partial = static_cast<float *>(workspace);
   }
   auto al = [](const void *p, int64_t ld) { return p == nullptr || ((uintptr_t)p % 16 == 0 && ld % 4 == 0); };
@@ -606,10 +602,8 @@ extern "C" int mgcn_input_layer_bwd(int64_t n_rows, int32_t F, const float *dZ, 
                    (!relu2 || (Z && ldz >= F && ldz % 4 == 0 && (uintptr_t)Z % 16 == 0)),
                "mgcn_input_layer_bwd: bad arguments (dZ / Z need 16-byte aligned rows)");
   const size_t need = mgcn_input_layer_bwd_workspace_bytes(n_rows, F);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("mgcn_input_layer_bwd: workspace %zu < %zu", workspace_bytes, need);
-    return MGCN_EWORKSPACE;
-  }
+  if (int rc = require_workspace("mgcn_input_layer_bwd", workspace, workspace_bytes, need))
+    return rc;
   const int nblk = colsum_blocks(n_rows);
   float *partial = static_cast<float *>(workspace);
   hipLaunchKernelGGL(input_layer_bwd_kernel, dim3(nblk), dim3(kBlock), 0, s, n_rows, (int)F, dZ,

@@ -2016,6 +2016,94 @@ extern "C" size_t mgcn_spmm_xw_fwd_workspace_bytes(int32_t F_in, int32_t F_out) 
   return F_in == 256 && F_out == 256 ? xw_wide_workspace_bytes(false) : 0;
 }
 
+// Host code the layer entry points share, dense and packed.  `who` is the
+// entry's name, as in check_packed: every message keeps its prefix.
+namespace {
+inline bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+// the last argument checks of a forward; wide: the 256-wide kernels (no bias
+// requirement, no ldz bound: 64-bit row bases)
+int check_fwd_outputs(const char *who, bool wide, int32_t F_in, const float *bias,
+                      const uint32_t *relu_mask, const float *Z, int64_t ldz) {
+  MGCN_REQUIRE(wide || bias == nullptr || reinterpret_cast<uintptr_t>(bias) % 4 == 0,
+               "%s: bias not 4-byte aligned", who);
+  MGCN_REQUIRE(relu_mask == nullptr || aligned16(relu_mask), "%s: relu_mask not 16-byte aligned",
+               who);
+  MGCN_REQUIRE(Z == nullptr || (ldz >= F_in && ldz % 4 == 0 && aligned16(Z) &&
+                                (wide || (uint64_t)kXwRows * (uint64_t)ldz * 4u < (1ull << 31))),
+               "%s: Z must have 16-byte aligned rows (ldz >= F_in)", who);
+  return MGCN_OK;
+}
+
+// the 128-wide forward's arguments but its table (X, ldx, n_cols, or fill_pk128)
+XwArgs xw_args(int64_t n_rows, const int64_t *rowptr, const int32_t *col, const float *w,
+               const float *W, int64_t ldw, const float *bias, float *Y, int64_t ldy, int reduce,
+               int relu, uint32_t *relu_mask, float *Z, int64_t ldz) {
+  XwArgs a{};
+  a.n_rows = n_rows;
+  a.rowptr = rowptr;
+  a.col = col;
+  a.w = w;
+  a.W = W;
+  a.ldw = ldw;
+  a.bias = bias;
+  a.Y = Y;
+  a.ldy = ldy;
+  a.relu_mask = relu_mask;
+  a.Z = Z;
+  a.ldz = ldz;
+  a.mean = reduce == MGCN_REDUCE_MEAN;
+  a.relu = relu != 0;
+  return a;
+}
+
+inline int epi_of(const uint32_t *relu_mask, const float *row_div) {
+  return relu_mask == nullptr ? EPI_STORE : row_div != nullptr ? EPI_RELU_DIV : EPI_RELU;
+}
+
+// the last argument checks of an adjoint: W / dX (wide: the 256-wide
+// kernels), the mask and the workspace
+int check_bwd_outputs(const char *who, bool wide, int64_t n_rows, int32_t F_in, int32_t F_out,
+                      const float *W, int64_t ldw, const float *dX, int64_t lddx,
+                      const uint32_t *relu_mask, const void *workspace, size_t workspace_bytes) {
+  if (wide)
+    MGCN_REQUIRE(W != nullptr && ldw >= F_out && lddx >= F_in && lddx % 4 == 0 && aligned16(dX) &&
+                     (uint64_t)16 * (uint64_t)lddx * 4u < (1ull << 31),
+                 "%s: bad W/dX (16-byte aligned dX rows)", who);
+  else  // the warp-specialised adjoint copies W into LDS with 16-byte loads
+    MGCN_REQUIRE(W == nullptr || (ldw % 4 == 0 && aligned16(W)),
+                 "%s: W must have 16-byte aligned rows", who);
+  MGCN_REQUIRE(relu_mask == nullptr || aligned16(relu_mask), "%s: relu_mask not 16-byte aligned",
+               who);
+  return require_workspace(who, workspace, workspace_bytes,
+                           mgcn_spmm_xw_bwd_workspace_bytes(n_rows, F_in, F_out));
+}
+
+// the 128-wide adjoint's arguments but its table (dY, lddy, n_cols, or
+// fill_pk128), X and the max adjoint's maps; the workspace split into the dW
+// and column-sum partials
+XbArgs xb_args(int64_t n_rows, const int64_t *rowptr_t, const int32_t *col_t, const float *w_t,
+               const float *row_scale, const float *W, int64_t ldw, float *dX, int64_t lddx,
+               const uint32_t *relu_mask, const float *row_div, void *workspace) {
+  XbArgs a{};
+  a.n_rows = n_rows;
+  a.rowptr = rowptr_t;
+  a.col = col_t;
+  a.w = w_t;
+  a.row_scale = row_scale;
+  a.W = W;
+  a.ldw = ldw;
+  a.dX = dX;
+  a.lddx = lddx;
+  a.relu_mask = relu_mask;
+  a.row_div = row_div;
+  a.dw_partial = static_cast<float *>(workspace);
+  a.colsum_partial = reinterpret_cast<float *>(static_cast<char *>(workspace) +
+                                               align_up((size_t)xw_grid() * kXwF * kXwF * 4, 256));
+  return a;
+}
+}  // namespace
+
 extern "C" int mgcn_spmm_xw_fwd(int64_t n_rows, int64_t n_cols, int32_t F_in, int32_t F_out,
                                 const int64_t *rowptr, const int32_t *col, const float *w,
                                 const float *X, int64_t ldx, const float *W, int64_t ldw,
@@ -2040,17 +2128,13 @@ extern "C" int mgcn_spmm_xw_fwd(int64_t n_rows, int64_t n_cols, int32_t F_in, in
     // no table-size limit; 32-bit offsets only within a 16-row chunk
     MGCN_REQUIRE(n_cols > 0 && (uint64_t)16 * (uint64_t)(ldy > ldz ? ldy : ldz) * 4u < (1ull << 31),
                  "mgcn_spmm_xw_fwd: leading dimension too large");
-    MGCN_REQUIRE(relu_mask == nullptr || reinterpret_cast<uintptr_t>(relu_mask) % 16 == 0,
-                 "mgcn_spmm_xw_fwd: relu_mask not 16-byte aligned");
-    MGCN_REQUIRE(Z == nullptr || (ldz >= F_in && ldz % 4 == 0 && reinterpret_cast<uintptr_t>(Z) % 16 == 0),
-                 "mgcn_spmm_xw_fwd: Z must have 16-byte aligned rows (ldz >= F_in)");
-    MGCN_REQUIRE(ldy % 4 == 0 && reinterpret_cast<uintptr_t>(Y) % 16 == 0,
+    if (int rc = check_fwd_outputs("mgcn_spmm_xw_fwd", true, F_in, bias, relu_mask, Z, ldz))
+      return rc;
+    MGCN_REQUIRE(ldy % 4 == 0 && aligned16(Y),
                  "mgcn_spmm_xw_fwd: Y must have 16-byte aligned rows at F = 256");
-    const size_t need = mgcn_spmm_xw_fwd_workspace_bytes(F_in, F_out);
-    if (workspace == nullptr || workspace_bytes < need) {
-      set_error("mgcn_spmm_xw_fwd: workspace %zu < %zu", workspace_bytes, need);
-      return MGCN_EWORKSPACE;
-    }
+    if (int rc = require_workspace("mgcn_spmm_xw_fwd", workspace, workspace_bytes,
+                                   mgcn_spmm_xw_fwd_workspace_bytes(F_in, F_out)))
+      return rc;
     return xw_wide_fwd(n_rows, rowptr, col, w, X, ldx, W, ldw, bias, Y, ldy,
                        reduce == MGCN_REDUCE_MEAN, relu != 0, relu_mask, Z, ldz, workspace,
                        as_stream(stream));
@@ -2059,31 +2143,12 @@ extern "C" int mgcn_spmm_xw_fwd(int64_t n_rows, int64_t n_cols, int32_t F_in, in
                "mgcn_spmm_xw_fwd: X must hold 1 .. 4 GiB - 1 bytes (32-bit gather offsets)");
   MGCN_REQUIRE((uint64_t)kXwRows * (uint64_t)ldy * 4u < (1ull << 31),
                "mgcn_spmm_xw_fwd: ldy too large");
-  MGCN_REQUIRE(bias == nullptr || reinterpret_cast<uintptr_t>(bias) % 4 == 0,
-               "mgcn_spmm_xw_fwd: bias not 4-byte aligned");
-  MGCN_REQUIRE(relu_mask == nullptr || reinterpret_cast<uintptr_t>(relu_mask) % 16 == 0,
-               "mgcn_spmm_xw_fwd: relu_mask not 16-byte aligned");
-  MGCN_REQUIRE(Z == nullptr || (ldz >= F_in && ldz % 4 == 0 && reinterpret_cast<uintptr_t>(Z) % 16 == 0 &&
-                                (uint64_t)kXwRows * (uint64_t)ldz * 4u < (1ull << 31)),
-               "mgcn_spmm_xw_fwd: Z must have 16-byte aligned rows (ldz >= F_in)");
-  XwArgs a{};
-  a.n_rows = n_rows;
-  a.rowptr = rowptr;
-  a.col = col;
-  a.w = w;
+  if (int rc = check_fwd_outputs("mgcn_spmm_xw_fwd", false, F_in, bias, relu_mask, Z, ldz))
+    return rc;
+  XwArgs a = xw_args(n_rows, rowptr, col, w, W, ldw, bias, Y, ldy, reduce, relu, relu_mask, Z, ldz);
   a.X = X;
   a.ldx = ldx;
   a.n_cols = n_cols;
-  a.W = W;
-  a.ldw = ldw;
-  a.bias = bias;
-  a.Y = Y;
-  a.ldy = ldy;
-  a.relu_mask = relu_mask;
-  a.Z = Z;
-  a.ldz = ldz;
-  a.mean = reduce == MGCN_REDUCE_MEAN;
-  a.relu = relu != 0;
   hipStream_t s = as_stream(stream);
   // (without the workspace -- callers from before it existed -- every chunk is static)
   int rc = MGCN_OK;
@@ -2137,7 +2202,7 @@ int xw_bwd_impl(int64_t n_rows, int64_t n_cols, int32_t F_in, int32_t F_out,
   }
   MGCN_REQUIRE(!dx_only || (dX != nullptr && win_mask == nullptr),
                "mgcn_spmm_xw_bwd: the dX-only form needs dX and takes no win_mask");
-  const int epi = relu_mask == nullptr ? EPI_STORE : row_div != nullptr ? EPI_RELU_DIV : EPI_RELU;
+  const int epi = epi_of(relu_mask, row_div);
   MGCN_REQUIRE(epi == EPI_STORE || (dX != nullptr && colsum != nullptr),
                "mgcn_spmm_xw_bwd: relu_mask needs dX and colsum");
   MGCN_REQUIRE(rowptr_t && dY, "mgcn_spmm_xw_bwd: null array");
@@ -2145,17 +2210,9 @@ int xw_bwd_impl(int64_t n_rows, int64_t n_cols, int32_t F_in, int32_t F_out,
                "mgcn_spmm_xw_bwd: dY must have 16-byte aligned rows");
   if (F_in == 256) {
     MGCN_REQUIRE(dX != nullptr && win_mask == nullptr, "mgcn_spmm_xw_bwd: the dX-only form needs dX");
-    MGCN_REQUIRE(W != nullptr && ldw >= F_out && lddx >= F_in && lddx % 4 == 0 &&
-                     reinterpret_cast<uintptr_t>(dX) % 16 == 0 &&
-                     (uint64_t)16 * (uint64_t)lddx * 4u < (1ull << 31),
-                 "mgcn_spmm_xw_bwd: bad W/dX (16-byte aligned dX rows)");
-    MGCN_REQUIRE(relu_mask == nullptr || reinterpret_cast<uintptr_t>(relu_mask) % 16 == 0,
-                 "mgcn_spmm_xw_bwd: relu_mask not 16-byte aligned");
-    const size_t need = mgcn_spmm_xw_bwd_workspace_bytes(n_rows, F_in, F_out);
-    if (workspace == nullptr || workspace_bytes < need) {
-      set_error("mgcn_spmm_xw_bwd: workspace %zu < %zu", workspace_bytes, need);
-      return MGCN_EWORKSPACE;
-    }
+    if (int rc = check_bwd_outputs("mgcn_spmm_xw_bwd", true, n_rows, F_in, F_out, W, ldw, dX, lddx,
+                                   relu_mask, workspace, workspace_bytes))
+      return rc;
     return xw_wide_bwd_dx(n_rows, rowptr_t, col_t, w_t, row_scale, dY, lddy, W, ldw, dX, lddx,
                           relu_mask, row_div, colsum, accumulate, workspace, s);
   }
@@ -2168,41 +2225,21 @@ int xw_bwd_impl(int64_t n_rows, int64_t n_cols, int32_t F_in, int32_t F_out,
                "mgcn_spmm_xw_bwd: leading dimension too large");
   MGCN_REQUIRE(dX == nullptr || (W != nullptr && ldw >= F_out && lddx >= F_in),
                "mgcn_spmm_xw_bwd: bad W/dX");
-  // the warp-specialised adjoint copies W into LDS with 16-byte loads
-  MGCN_REQUIRE(W == nullptr || (ldw % 4 == 0 && reinterpret_cast<uintptr_t>(W) % 16 == 0),
-               "mgcn_spmm_xw_bwd: W must have 16-byte aligned rows");
-  MGCN_REQUIRE(relu_mask == nullptr || reinterpret_cast<uintptr_t>(relu_mask) % 16 == 0,
-               "mgcn_spmm_xw_bwd: relu_mask not 16-byte aligned");
-  const size_t need = mgcn_spmm_xw_bwd_workspace_bytes(n_rows, F_in, F_out);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("mgcn_spmm_xw_bwd: workspace %zu < %zu", workspace_bytes, need);
-    return MGCN_EWORKSPACE;
-  }
+  if (int rc = check_bwd_outputs("mgcn_spmm_xw_bwd", false, n_rows, F_in, F_out, W, ldw, dX, lddx,
+                                 relu_mask, workspace, workspace_bytes))
+    return rc;
   const int64_t n_chunks = (n_rows + kXwRows - 1) / kXwRows;
   int grid = xw_grid();
   if (grid > n_chunks) grid = (int)n_chunks;
-  XbArgs a{};
-  a.n_rows = n_rows;
-  a.rowptr = rowptr_t;
-  a.col = col_t;
-  a.w = w_t;
-  a.row_scale = row_scale;
+  XbArgs a = xb_args(n_rows, rowptr_t, col_t, w_t, row_scale, W, ldw, dX, lddx, relu_mask, row_div,
+                     workspace);
   a.dY = dY;
   a.lddy = lddy;
   a.n_cols = n_cols;
   a.X = X;
   a.ldx = ldx;
-  a.W = W;
-  a.ldw = ldw;
-  a.dX = dX;
-  a.lddx = lddx;
-  a.relu_mask = relu_mask;
-  a.row_div = row_div;
   a.win_mask = win_mask;
   a.slot_map = slot_map;
-  a.dw_partial = static_cast<float *>(workspace);
-  a.colsum_partial = reinterpret_cast<float *>(static_cast<char *>(workspace) +
-                                               align_up((size_t)xw_grid() * kXwF * kXwF * 4, 256));
   int rc;
   if (dx_only) {
     rc = g_xw_unroll == 8 ? launch_xb_dx<8>(a, epi, grid, s) : launch_xb_dx<4>(a, epi, grid, s);
@@ -2345,28 +2382,10 @@ extern "C" int mgcn_spmm_xw_fwd_packed(int64_t n_rows, int32_t F_in, int32_t F_o
   if (F_in == kXwF) {
     MGCN_REQUIRE(ldw >= F_out && ldy >= F_out && (uint64_t)kXwRows * (uint64_t)ldy * 4u < (1ull << 31),
                  "mgcn_spmm_xw_fwd_packed: bad ldw / ldy");
-    MGCN_REQUIRE(bias == nullptr || reinterpret_cast<uintptr_t>(bias) % 4 == 0,
-                 "mgcn_spmm_xw_fwd_packed: bias not 4-byte aligned");
-    MGCN_REQUIRE(relu_mask == nullptr || reinterpret_cast<uintptr_t>(relu_mask) % 16 == 0,
-                 "mgcn_spmm_xw_fwd_packed: relu_mask not 16-byte aligned");
-    MGCN_REQUIRE(Z == nullptr || (ldz >= F_in && ldz % 4 == 0 && reinterpret_cast<uintptr_t>(Z) % 16 == 0 &&
-                                  (uint64_t)kXwRows * (uint64_t)ldz * 4u < (1ull << 31)),
-                 "mgcn_spmm_xw_fwd_packed: Z must have 16-byte aligned rows (ldz >= F_in)");
-    XwArgs a{};
-    a.n_rows = n_rows;
-    a.rowptr = rowptr;
-    a.col = col;
-    a.w = w;
-    a.W = W;
-    a.ldw = ldw;
-    a.bias = bias;
-    a.Y = Y;
-    a.ldy = ldy;
-    a.relu_mask = relu_mask;
-    a.Z = Z;
-    a.ldz = ldz;
-    a.mean = reduce == MGCN_REDUCE_MEAN;
-    a.relu = relu != 0;
+    if (int rc = check_fwd_outputs("mgcn_spmm_xw_fwd_packed", false, F_in, bias, relu_mask, Z, ldz))
+      return rc;
+    XwArgs a = xw_args(n_rows, rowptr, col, w, W, ldw, bias, Y, ldy, reduce, relu, relu_mask, Z,
+                       ldz);
     fill_pk128(a, X);
     hipStream_t s = as_stream(stream);
     // (the product build instantiates U = 3 only)
@@ -2380,15 +2399,11 @@ extern "C" int mgcn_spmm_xw_fwd_packed(int64_t n_rows, int32_t F_in, int32_t F_o
                    reinterpret_cast<uintptr_t>(Y) % 16 == 0 &&
                    (uint64_t)16 * (uint64_t)(ldy > ldz ? ldy : ldz) * 4u < (1ull << 31),
                "mgcn_spmm_xw_fwd_packed: Y must have 16-byte aligned rows");
-  MGCN_REQUIRE(relu_mask == nullptr || reinterpret_cast<uintptr_t>(relu_mask) % 16 == 0,
-               "mgcn_spmm_xw_fwd_packed: relu_mask not 16-byte aligned");
-  MGCN_REQUIRE(Z == nullptr || (ldz >= F_in && ldz % 4 == 0 && reinterpret_cast<uintptr_t>(Z) % 16 == 0),
-               "mgcn_spmm_xw_fwd_packed: Z must have 16-byte aligned rows (ldz >= F_in)");
-  const size_t need = mgcn_spmm_xw_fwd_workspace_bytes(F_in, F_out);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("mgcn_spmm_xw_fwd_packed: workspace %zu < %zu", workspace_bytes, need);
-    return MGCN_EWORKSPACE;
-  }
+  if (int rc = check_fwd_outputs("mgcn_spmm_xw_fwd_packed", true, F_in, bias, relu_mask, Z, ldz))
+    return rc;
+  if (int rc = require_workspace("mgcn_spmm_xw_fwd_packed", workspace, workspace_bytes,
+                                 mgcn_spmm_xw_fwd_workspace_bytes(F_in, F_out)))
+    return rc;
   return xw_wide_fwd(n_rows, rowptr, col, w, nullptr, 0, W, ldw, bias, Y, ldy,
                      reduce == MGCN_REDUCE_MEAN, relu != 0, relu_mask, Z, ldz, workspace,
                      as_stream(stream), X);
@@ -2420,34 +2435,15 @@ extern "C" int mgcn_spmm_xw_bwd_packed(int64_t n_rows, int32_t F_in, int32_t F_o
   if (F_in == kXwF) {
     MGCN_REQUIRE(ldw >= F_out && lddx >= F_in && (uint64_t)kXwRows * (uint64_t)lddx * 4u < (1ull << 31),
                  "mgcn_spmm_xw_bwd_packed: bad W/dX");
-    MGCN_REQUIRE(ldw % 4 == 0 && reinterpret_cast<uintptr_t>(W) % 16 == 0,
-                 "mgcn_spmm_xw_bwd_packed: W must have 16-byte aligned rows");
-    MGCN_REQUIRE(relu_mask == nullptr || reinterpret_cast<uintptr_t>(relu_mask) % 16 == 0,
-                 "mgcn_spmm_xw_bwd_packed: relu_mask not 16-byte aligned");
-    const size_t need = mgcn_spmm_xw_bwd_workspace_bytes(n_rows, F_in, F_out);
-    if (workspace == nullptr || workspace_bytes < need) {
-      set_error("mgcn_spmm_xw_bwd_packed: workspace %zu < %zu", workspace_bytes, need);
-      return MGCN_EWORKSPACE;
-    }
-    const int epi = relu_mask == nullptr ? EPI_STORE : row_div != nullptr ? EPI_RELU_DIV : EPI_RELU;
+    if (int rc = check_bwd_outputs("mgcn_spmm_xw_bwd_packed", false, n_rows, F_in, F_out, W, ldw,
+                                   dX, lddx, relu_mask, workspace, workspace_bytes))
+      return rc;
+    const int epi = epi_of(relu_mask, row_div);
     const int64_t n_chunks = (n_rows + kXwRows - 1) / kXwRows;
     int grid = xw_grid();
     if (grid > n_chunks) grid = (int)n_chunks;
-    XbArgs a{};
-    a.n_rows = n_rows;
-    a.rowptr = rowptr_t;
-    a.col = col_t;
-    a.w = w_t;
-    a.row_scale = row_scale;
-    a.W = W;
-    a.ldw = ldw;
-    a.dX = dX;
-    a.lddx = lddx;
-    a.relu_mask = relu_mask;
-    a.row_div = row_div;
-    a.dw_partial = static_cast<float *>(workspace);
-    a.colsum_partial = reinterpret_cast<float *>(static_cast<char *>(workspace) +
-                                                 align_up((size_t)xw_grid() * kXwF * kXwF * 4, 256));
+    XbArgs a = xb_args(n_rows, rowptr_t, col_t, w_t, row_scale, W, ldw, dX, lddx, relu_mask,
+                       row_div, workspace);
     fill_pk128(a, dY);
     constexpr bool X = MGCN_EXPERIMENT;  // (the product build instantiates U = 3 only)
     int rc;
@@ -2460,17 +2456,9 @@ extern "C" int mgcn_spmm_xw_bwd_packed(int64_t n_rows, int32_t F_in, int32_t F_o
     if (rc || epi == EPI_STORE) return rc;
     return launch_fold(a.colsum_partial, grid, kXwF, kXwF, colsum, kXwF, accumulate, s);
   }
-  MGCN_REQUIRE(ldw >= F_out && lddx >= F_in && lddx % 4 == 0 &&
-                   reinterpret_cast<uintptr_t>(dX) % 16 == 0 &&
-                   (uint64_t)16 * (uint64_t)lddx * 4u < (1ull << 31),
-               "mgcn_spmm_xw_bwd_packed: bad W/dX (16-byte aligned dX rows)");
-  MGCN_REQUIRE(relu_mask == nullptr || reinterpret_cast<uintptr_t>(relu_mask) % 16 == 0,
-               "mgcn_spmm_xw_bwd_packed: relu_mask not 16-byte aligned");
-  const size_t need = mgcn_spmm_xw_bwd_workspace_bytes(n_rows, F_in, F_out);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("mgcn_spmm_xw_bwd_packed: workspace %zu < %zu", workspace_bytes, need);
-    return MGCN_EWORKSPACE;
-  }
+  if (int rc = check_bwd_outputs("mgcn_spmm_xw_bwd_packed", true, n_rows, F_in, F_out, W, ldw, dX,
+                                 lddx, relu_mask, workspace, workspace_bytes))
+    return rc;
   return xw_wide_bwd_dx(n_rows, rowptr_t, col_t, w_t, row_scale, nullptr, 0, W, ldw, dX, lddx,
                         relu_mask, row_div, colsum, accumulate, workspace, s, dY);
 }

@@ -708,10 +708,7 @@ int gemm_tn_core(int64_t K, int32_t M, int32_t N, const float *A, int64_t lda, c
   const int tiles_m = (M + kTile - 1) / kTile, tiles_n = (N + kTile - 1) / kTile;
   const int splits = gemm_splits(K, M, N);
   const size_t need = mgcn_gemm_tn_workspace_bytes(K, M, N);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("mgcn_gemm_tn: workspace %zu < %zu", workspace_bytes, need);
-    return MGCN_EWORKSPACE;
-  }
+  if (int rc = require_workspace("mgcn_gemm_tn", workspace, workspace_bytes, need)) return rc;
   int64_t kps = (K + splits - 1) / splits;
   kps = (kps + 63) / 64 * 64;  // whole chunks of every variant (and whole kU groups)
   const int used = (int)((K + kps - 1) / kps);
@@ -1559,10 +1556,7 @@ extern "C" int mgcn_gemm_nn(int64_t M, int32_t K, int32_t N, const float *A, int
   float *partial = nullptr;
   if (epi != EPI_STORE) {
     const size_t need = mgcn_gemm_nn_workspace_bytes(M, N);
-    if (workspace == nullptr || workspace_bytes < need) {
-      set_error("mgcn_gemm_nn: workspace %zu < %zu", workspace_bytes, need);
-      return MGCN_EWORKSPACE;
-    }
+    if (int rc = require_workspace("mgcn_gemm_nn", workspace, workspace_bytes, need)) return rc;
     partial = static_cast<float *>(workspace);
   }
   int rc;
@@ -1967,10 +1961,7 @@ extern "C" int mgcn_gemm_bwd(int64_t M, int32_t F_in, int32_t F_out, const float
   MGCN_REQUIRE(dX == nullptr || (W != nullptr && ldw >= F_out && lddx >= F_in),
                "mgcn_gemm_bwd: bad W/dX");
   const size_t need = mgcn_gemm_bwd_workspace_bytes(M, F_in, F_out);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("mgcn_gemm_bwd: workspace %zu < %zu", workspace_bytes, need);
-    return MGCN_EWORKSPACE;
-  }
+  if (int rc = require_workspace("mgcn_gemm_bwd", workspace, workspace_bytes, need)) return rc;
   float *dwp = static_cast<float *>(workspace);
   float *csp = reinterpret_cast<float *>(static_cast<char *>(workspace) +
                                          align_up((size_t)kBwGrid * F_in * F_out * 4, 256));
@@ -2029,10 +2020,8 @@ extern "C" int mgcn_gemm_bwd_dw_cs(int64_t M, const float *X, int64_t ldx, const
                    reinterpret_cast<uintptr_t>(S) % 16 == 0,
                "mgcn_gemm_bwd_dw_cs: X / dH / S must be 16-byte aligned rows");
   const size_t need = mgcn_gemm_bwd_dw_cs_workspace_bytes(M);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("mgcn_gemm_bwd_dw_cs: workspace %zu < %zu", workspace_bytes, need);
-    return MGCN_EWORKSPACE;
-  }
+  if (int rc = require_workspace("mgcn_gemm_bwd_dw_cs", workspace, workspace_bytes, need))
+    return rc;
   float *dwp = static_cast<float *>(workspace);
   float *csp = reinterpret_cast<float *>(static_cast<char *>(workspace) +
                                          align_up((size_t)kBwGrid * kBwF * kBwF * 4, 256));

@@ -75,6 +75,13 @@ inline int check_launch(const char *what) {
     }                                 \
   } while (0)
 
+// MGCN_EWORKSPACE ("<who>: workspace <given> < <need>") unless `workspace` holds `need` bytes
+inline int require_workspace(const char *who, const void *workspace, size_t bytes, size_t need) {
+  if (workspace != nullptr && bytes >= need) return MGCN_OK;
+  set_error("%s: workspace %zu < %zu", who, bytes, need);
+  return MGCN_EWORKSPACE;
+}
+
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Grid sizing for grid-stride loops over memory-bound work: enough blocks to

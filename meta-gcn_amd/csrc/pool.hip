@@ -239,10 +239,8 @@ extern "C" int mgcn_edge_merge_greedy(int64_t n_nodes, int64_t n_edges, const in
   MGCN_REQUIRE(n_nodes == 0 || cluster != nullptr, "mgcn_edge_merge_greedy: null cluster");
   MGCN_REQUIRE(n_edges == 0 || n_nodes > 0, "mgcn_edge_merge_greedy: edges without nodes");
   const size_t need = mgcn_edge_merge_workspace_bytes(n_nodes, n_edges);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("mgcn_edge_merge_greedy: workspace %zu < %zu", workspace_bytes, need);
-    return MGCN_EWORKSPACE;
-  }
+  if (int rc = require_workspace("mgcn_edge_merge_greedy", workspace, workspace_bytes, need))
+    return rc;
   hipStream_t s = as_stream(stream);
   int32_t *rank = static_cast<int32_t *>(workspace);
   int32_t *flag = rank + n_edges;

@@ -722,10 +722,8 @@ extern "C" int mgcn_residual_layer_bwd(int64_t n_rows, int32_t F, const int64_t 
   MGCN_REQUIRE(order == nullptr || (0 <= n_giant && n_giant <= n_heavy && n_heavy <= n_rows),
                "mgcn_residual_layer_bwd: need 0 <= n_giant <= n_heavy <= n_rows");
   const size_t need = mgcn_residual_layer_bwd_workspace_bytes(n_rows, F);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("mgcn_residual_layer_bwd: workspace %zu < %zu", workspace_bytes, need);
-    return MGCN_EWORKSPACE;
-  }
+  if (int rc = require_workspace("mgcn_residual_layer_bwd", workspace, workspace_bytes, need))
+    return rc;
   float *dA = static_cast<float *>(workspace);
   float *partial = reinterpret_cast<float *>(static_cast<char *>(workspace) +
                                              align_up((size_t)n_rows * F * sizeof(float), 256));
@@ -816,10 +814,8 @@ extern "C" int mgcn_residual_stack_bwd(int64_t n_rows, int32_t F, int32_t n_laye
   MGCN_REQUIRE(W && Wr && dW && dWr && sums && relu1 && relu2 && masks && Z && dZ && X0,
                "mgcn_residual_stack_bwd: null array");
   const StackScratch sc = stack_scratch(n_rows, F);
-  if (workspace == nullptr || workspace_bytes < sc.total) {
-    set_error("mgcn_residual_stack_bwd: workspace %zu < %zu", workspace_bytes, sc.total);
-    return MGCN_EWORKSPACE;
-  }
+  if (int rc = require_workspace("mgcn_residual_stack_bwd", workspace, workspace_bytes, sc.total))
+    return rc;
   char *ws = static_cast<char *>(workspace);
   float *dAb[2] = {reinterpret_cast<float *>(ws + sc.da), reinterpret_cast<float *>(ws + sc.da + sc.nf)};
   float *DHb[2] = {reinterpret_cast<float *>(ws + sc.dh), reinterpret_cast<float *>(ws + sc.dh + sc.n2f)};

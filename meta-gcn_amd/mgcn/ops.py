@@ -18,19 +18,36 @@ from __future__ import annotations
 
 import enum
 import os
-from collections import Counter
 from dataclasses import dataclass
 
 import torch
 
+from . import _call
 from . import _lib as L
+from ._call import _aligned_rows, _contig_f32, launch, set_kernel_timer, workspace  # noqa: F401
 from .graph import CSRView, GraphPlan, NormPlan, plan_for
+# The layers below this module (the launch path): every name they
+# define stays importable from here.
+from .ops_gemm import (SMALL_K, VENDOR_GEMMS, _Bmm, _bstr, _gemm_batched,  # noqa: F401
+                       _Linear, _LinearBias, _mm, _mm_t, bmm, dw_pass, dw_pass_cs,
+                       dw_pass_supported, gemm_bwd, gemm_bwd_supported, gemm_nn,
+                       gemm_nn_epi_supported, gemm_nn_supported, gemm_small_k, gemm_tn,
+                       gemm_tn_split, linear, linear_bias, make_relu_mask, mm_route,
+                       relu_bwd_colsum)
+from .ops_attention import (_AttentionAggregate, _HardAttentionEval,  # noqa: F401
+                            _HardAttentionTrain, attention_aggregate,
+                            hard_attention_aggregate)
+from .ops_pack import (PACK_ROWS_WIDTHS, PackedTable, _SegmentMean, pack_rows,  # noqa: F401
+                       pack_rows_count, pack_rows_values, packed_cols, packed_row_bits,
+                       segment_mean, unpack_rows)
 
 
-# optional callable(name, start: bool, rows=None, edges=None) called right
-# before / after each libmgcn launch on its stream (bench.py's HIP-event timer);
-# the start call carries the launch's row and edge counts for byte accounting
-_TIMER = None
+def __getattr__(name):
+    if name == "_TIMER":  # the hook's home is _call
+        return _call._TIMER
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 # fused aggregate-then-transform forward for 128 -> 128 sum / mean layers
 # (mgcn_spmm_xw_fwd); MGCN_FUSE_XW=0 selects the GEMM + SpMM launches
 _FUSE_XW = os.environ.get("MGCN_FUSE_XW", "1") != "0"
@@ -58,23 +75,6 @@ def set_z_middle(enabled: bool) -> None:
     gather kernel (False, the default)."""
     global _Z_MIDDLE
     _Z_MIDDLE = bool(enabled)
-
-
-def set_kernel_timer(timer) -> None:
-    """Install (or clear with None) a hook called right before and after each
-    libmgcn launch, on the launch stream -- used to time kernels with events."""
-    global _TIMER
-    _TIMER = timer
-
-
-def _contig_f32(t: torch.Tensor, name: str) -> torch.Tensor:
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32 (the reference computes in fp32), got {t.dtype}")
-    if t.dim() != 2:
-        raise ValueError(f"{name} must be 2-D [N, F], got {tuple(t.shape)}")
-    if t.stride(1) != 1 or t.stride(0) < t.size(1):
-        t = t.contiguous()
-    return t
 
 
 def spmm_fwd(view: CSRView, w: torch.Tensor | None, H: torch.Tensor, reduce: int,
@@ -106,17 +106,11 @@ def spmm_fwd(view: CSRView, w: torch.Tensor | None, H: torch.Tensor, reduce: int
         bias = bias.detach().to(torch.float32).contiguous()
         if bias.numel() != F:
             raise ValueError(f"bias has {bias.numel()} entries, expected {F}")
-    if _TIMER is not None:
-        _TIMER("spmm_fwd", True, view.n_rows, view.edges)
-    with L.device_guard(dev):
-        rc = lib.mgcn_spmm_fwd(view.n_rows, F, L.ptr(view.rowptr), L.ptr(view.col),
-                               L.ptr(view.eid), L.ptr(w), L.ptr(H), H.stride(0), L.ptr(Y),
-                               Y.stride(0), reduce, L.ptr(bias), int(bool(relu)), L.ptr(argmax),
-                               L.ptr(mask), L.ptr(relu_mask), L.ptr(view.order), view.n_heavy,
-                               view.n_giant, L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("spmm_fwd", False)
-    L.check(rc, "mgcn_spmm_fwd")
+    launch("spmm_fwd", "mgcn_spmm_fwd", dev, view.n_rows, view.edges, lib.mgcn_spmm_fwd,
+           view.n_rows, F, L.ptr(view.rowptr), L.ptr(view.col), L.ptr(view.eid), L.ptr(w),
+           L.ptr(H), H.stride(0), L.ptr(Y), Y.stride(0), reduce, L.ptr(bias), int(bool(relu)),
+           L.ptr(argmax), L.ptr(mask), L.ptr(relu_mask), L.ptr(view.order), view.n_heavy,
+           view.n_giant, L.stream_of(dev))
     return Y, (mask if mask is not None else argmax)
 
 
@@ -182,9 +176,7 @@ def spmm_xw_fwd(view: CSRView, w: torch.Tensor | None, X: torch.Tensor, W: torch
     lib = L.load()
     packed = isinstance(X, PackedTable)
     if not packed:
-        X = _contig_f32(X, "X")
-        if X.stride(0) % 4 or X.data_ptr() % 16:
-            X = X.contiguous()
+        X = _aligned_rows(X, "X")
     W = W.detach()
     dev = L.require_device(X.words if packed else X, W, view.rowptr, w, bias, relu_mask)
     F_in, F_out = W.shape
@@ -222,30 +214,21 @@ def spmm_xw_fwd(view: CSRView, w: torch.Tensor | None, X: torch.Tensor, W: torch
                               or t.data_ptr() % 16):
             raise ValueError(f"spmm_xw_fwd: {name} must be float32 [{view.n_rows}, {f}] with "
                              f"16-byte aligned rows")
-    ws_bytes = int(lib.mgcn_spmm_xw_fwd_workspace_bytes(F_in, F_out))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    ws, ws_bytes = workspace(lib.mgcn_spmm_xw_fwd_workspace_bytes(F_in, F_out), dev, or_null=True)
     tname = ("spmm_xw_fwd_z" if want_z else "spmm_xw_fwd") + ("_pk" if packed else "")
-    if _TIMER is not None:
-        _TIMER(tname, True, view.n_rows, view.edges)
-    with L.device_guard(dev):
-        if packed:
-            pk = X.c_struct()
-            rc = lib.mgcn_spmm_xw_fwd_packed(view.n_rows, F_in, F_out, L.ptr(view.rowptr),
-                                             L.ptr(view.col), L.ptr(w), L.byref(pk), L.ptr(W),
-                                             W.stride(0), L.ptr(bias), L.ptr(Y), Y.stride(0),
-                                             reduce, int(bool(relu)), L.ptr(relu_mask), L.ptr(Z),
-                                             Z.stride(0) if Z is not None else 0, L.ptr(ws),
-                                             ws_bytes, L.stream_of(dev))
-        else:
-            rc = lib.mgcn_spmm_xw_fwd(view.n_rows, view.n_cols, F_in, F_out, L.ptr(view.rowptr),
-                                      L.ptr(view.col), L.ptr(w), L.ptr(X), X.stride(0), L.ptr(W),
-                                      W.stride(0), L.ptr(bias), L.ptr(Y), Y.stride(0), reduce,
-                                      int(bool(relu)), L.ptr(relu_mask), L.ptr(Z),
-                                      Z.stride(0) if Z is not None else 0, L.ptr(ws), ws_bytes,
-                                      L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER(tname, False)
-    L.check(rc, "mgcn_spmm_xw_fwd_packed" if packed else "mgcn_spmm_xw_fwd")
+    # after the table (the dense one with its row count), both entries take the same arguments
+    tail = (L.ptr(W), W.stride(0), L.ptr(bias), L.ptr(Y), Y.stride(0), reduce, int(bool(relu)),
+            L.ptr(relu_mask), L.ptr(Z), Z.stride(0) if Z is not None else 0, L.ptr(ws), ws_bytes,
+            L.stream_of(dev))
+    if packed:
+        pk = X.c_struct()
+        launch(tname, "mgcn_spmm_xw_fwd_packed", dev, view.n_rows, view.edges,
+               lib.mgcn_spmm_xw_fwd_packed, view.n_rows, F_in, F_out, L.ptr(view.rowptr),
+               L.ptr(view.col), L.ptr(w), L.byref(pk), *tail)
+    else:
+        launch(tname, "mgcn_spmm_xw_fwd", dev, view.n_rows, view.edges, lib.mgcn_spmm_xw_fwd,
+               view.n_rows, view.n_cols, F_in, F_out, L.ptr(view.rowptr), L.ptr(view.col),
+               L.ptr(w), L.ptr(X), X.stride(0), *tail)
     return (Y, Z) if want_z else Y
 
 
@@ -267,43 +250,49 @@ def spmm_xw_bwd(view_t: CSRView, w_t: torch.Tensor | None, row_scale: torch.Tens
     (dW, dX or None, colsum or None).  ``dY`` may be a :class:`PackedTable`
     (128- or 256-wide, dX-only form X = None; ``mgcn_spmm_xw_bwd_packed``)."""
     lib = L.load()
-    if isinstance(dY, PackedTable):
-        return _spmm_xw_bwd_packed(view_t, w_t, row_scale, dY, X, W, want_dx, relu_mask, row_div,
-                                   win_mask, dx_out, colsum_acc, dy_colsum_out)
-    dY = _contig_f32(dY, "dY")
-    if dY.stride(0) % 4 or dY.data_ptr() % 16:
-        dY = dY.contiguous()
+    packed = isinstance(dY, PackedTable)
     dx_only = X is None  # dW formed by the caller (Z^T dY, :func:`gemm_bwd`)
-    if not dx_only:
-        X = _contig_f32(X, "X")
-        if X.stride(0) % 4 or X.data_ptr() % 16:
-            X = X.contiguous()
+    if packed:
+        if not dx_only or not want_dx or win_mask is not None or dy_colsum_out is not None:
+            raise ValueError("spmm_xw_bwd: a packed dY takes the dX-only form (X = None, no max)")
+    else:
+        dY = _aligned_rows(dY, "dY")
+        if not dx_only:
+            X = _aligned_rows(X, "X")
     W = W.detach()
     # (the warp-specialised adjoint copies W into LDS with 16-byte loads)
     if W.dtype != torch.float32 or W.stride(1) != 1 or W.stride(0) % 4 or W.data_ptr() % 16:
         W = W.to(torch.float32).contiguous()
-    dev = L.require_device(dY, X, W, view_t.rowptr, w_t, row_scale, relu_mask, row_div)
+    dev = L.require_device(dY.words if packed else dY, X, W, view_t.rowptr, w_t, row_scale,
+                           relu_mask, row_div)
     F_in, F_out = W.shape
     M = view_t.n_rows if dx_only else X.size(0)
-    if dx_only and (not want_dx or win_mask is not None):
-        raise ValueError("spmm_xw_bwd: X=None (dX only) needs want_dx and no win_mask")
-    if (not dx_only and X.size(1) != F_in) or M != view_t.n_rows or \
-            dY.size(0) != view_t.n_cols or dY.size(1) != F_out:
-        raise ValueError(f"spmm_xw_bwd: X {None if dx_only else tuple(X.shape)}, dY "
-                         f"{tuple(dY.shape)} do not fit the "
-                         f"graph ({view_t.n_rows} sources, {view_t.n_cols} destinations)")
-    if (win_mask is None) != (slot_map is None):
-        raise ValueError("spmm_xw_bwd: win_mask and slot_map go together (max adjoint)")
-    if win_mask is not None and (win_mask.dtype != torch.int32 or win_mask.dim() != 2
-                                 or win_mask.size(1) != (F_out + 31) // 32):
-        raise ValueError("spmm_xw_bwd: win_mask must be int32 [nnz, ceil(F/32)]")
+    if packed:
+        if dY.F != F_out:
+            raise ValueError(f"spmm_xw_bwd: packed dY of F = {dY.F}, W is [{F_in}, {F_out}]")
+    else:
+        if dx_only and (not want_dx or win_mask is not None):
+            raise ValueError("spmm_xw_bwd: X=None (dX only) needs want_dx and no win_mask")
+        if (not dx_only and X.size(1) != F_in) or M != view_t.n_rows or \
+                dY.size(0) != view_t.n_cols or dY.size(1) != F_out:
+            raise ValueError(f"spmm_xw_bwd: X {None if dx_only else tuple(X.shape)}, dY "
+                             f"{tuple(dY.shape)} do not fit the "
+                             f"graph ({view_t.n_rows} sources, {view_t.n_cols} destinations)")
+        if (win_mask is None) != (slot_map is None):
+            raise ValueError("spmm_xw_bwd: win_mask and slot_map go together (max adjoint)")
+        if win_mask is not None and (win_mask.dtype != torch.int32 or win_mask.dim() != 2
+                                     or win_mask.size(1) != (F_out + 31) // 32):
+            raise ValueError("spmm_xw_bwd: win_mask must be int32 [nnz, ceil(F/32)]")
     dW = None if dx_only else torch.empty(F_in, F_out, dtype=torch.float32, device=dev)
     dX = None
     if want_dx:
         dX = dx_out if dx_out is not None else torch.empty(M, F_in, dtype=torch.float32,
                                                            device=dev)
-        if (dX.dtype != torch.float32 or dX.dim() != 2 or tuple(dX.shape) != (M, F_in) or
-                dX.stride(1) != 1 or dX.stride(0) < F_in):
+        ok = (dX.dtype == torch.float32 and dX.dim() == 2 and tuple(dX.shape) == (M, F_in) and
+              dX.stride(1) == 1)
+        if packed and (not ok or dX.stride(0) % 4 or dX.data_ptr() % 16):
+            raise ValueError(f"spmm_xw_bwd: dx_out must be float32 [{M}, {F_in}], 16-byte rows")
+        if not packed and (not ok or dX.stride(0) < F_in):
             raise ValueError(f"spmm_xw_bwd: dx_out must be float32 [{M}, {F_in}], row-major")
     colsum = None
     if relu_mask is not None:
@@ -332,83 +321,29 @@ def spmm_xw_bwd(view_t: CSRView, w_t: torch.Tensor | None, row_scale: torch.Tens
             raise ValueError("spmm_xw_bwd: dy_colsum_out needs the dW + dX form of a square "
                              f"graph (no max) and a contiguous float32 [{F_out}] tensor")
         L.require_device(dy_colsum_out)
-    ws_bytes = int(lib.mgcn_spmm_xw_bwd_workspace_bytes(M, F_in, F_out))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    tname = "spmm_xw_bwd_dx" if dx_only else "spmm_xw_bwd" if want_dx else "spmm_xw_bwd_dw"
-    if _TIMER is not None:
-        _TIMER(tname, True, view_t.n_rows, view_t.edges)
-    if dy_colsum_out is not None:
-        with L.device_guard(dev):
-            rc = lib.mgcn_spmm_xw_bwd_hcs(M, view_t.n_cols, L.ptr(view_t.rowptr), L.ptr(view_t.col),
-                                          L.ptr(w_t), L.ptr(row_scale), L.ptr(dY), dY.stride(0),
-                                          L.ptr(X), X.stride(0), L.ptr(W), W.stride(0), L.ptr(dW),
-                                          dW.stride(0), 0, L.ptr(dX), dX.stride(0),
-                                          L.ptr(relu_mask), L.ptr(row_div), L.ptr(colsum),
-                                          L.ptr(dy_colsum_out), L.ptr(ws), ws_bytes,
-                                          L.stream_of(dev))
-        if _TIMER is not None:
-            _TIMER(tname, False)
-        L.check(rc, "mgcn_spmm_xw_bwd_hcs")
-        return dW, dX, colsum
-    with L.device_guard(dev):
-        rc = lib.mgcn_spmm_xw_bwd(M, view_t.n_cols, F_in, F_out, L.ptr(view_t.rowptr),
-                                  L.ptr(view_t.col), L.ptr(w_t), L.ptr(row_scale), L.ptr(dY),
-                                  dY.stride(0), L.ptr(X), 0 if dx_only else X.stride(0),
-                                  L.ptr(W), W.stride(0), L.ptr(dW),
-                                  0 if dx_only else dW.stride(0), acc_flag, L.ptr(dX),
-                                  dX.stride(0) if dX is not None else 0, L.ptr(relu_mask),
-                                  L.ptr(row_div), L.ptr(colsum), L.ptr(win_mask),
-                                  L.ptr(slot_map), L.ptr(ws), ws_bytes, L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER(tname, False)
-    L.check(rc, "mgcn_spmm_xw_bwd")
+    ws, ws_bytes = workspace(lib.mgcn_spmm_xw_bwd_workspace_bytes(M, F_in, F_out), dev)
+    graph = (L.ptr(view_t.rowptr), L.ptr(view_t.col), L.ptr(w_t), L.ptr(row_scale))
+    epi = (L.ptr(relu_mask), L.ptr(row_div), L.ptr(colsum))
+    if packed:
+        tname, sym = "spmm_xw_bwd_dx_pk", "mgcn_spmm_xw_bwd_packed"
+        pk = dY.c_struct()
+        args = (M, F_in, F_out, *graph, L.byref(pk), L.ptr(W), W.stride(0), L.ptr(dX),
+                dX.stride(0), *epi, acc_flag)
+    elif dy_colsum_out is not None:
+        tname, sym = "spmm_xw_bwd", "mgcn_spmm_xw_bwd_hcs"
+        args = (M, view_t.n_cols, *graph, L.ptr(dY), dY.stride(0), L.ptr(X), X.stride(0),
+                L.ptr(W), W.stride(0), L.ptr(dW), dW.stride(0), 0, L.ptr(dX), dX.stride(0), *epi,
+                L.ptr(dy_colsum_out))
+    else:
+        tname = "spmm_xw_bwd_dx" if dx_only else "spmm_xw_bwd" if want_dx else "spmm_xw_bwd_dw"
+        sym = "mgcn_spmm_xw_bwd"
+        args = (M, view_t.n_cols, F_in, F_out, *graph, L.ptr(dY), dY.stride(0), L.ptr(X),
+                0 if dx_only else X.stride(0), L.ptr(W), W.stride(0), L.ptr(dW),
+                0 if dx_only else dW.stride(0), acc_flag, L.ptr(dX),
+                dX.stride(0) if dX is not None else 0, *epi, L.ptr(win_mask), L.ptr(slot_map))
+    launch(tname, sym, dev, view_t.n_rows, view_t.edges, getattr(lib, sym), *args, L.ptr(ws),
+           ws_bytes, L.stream_of(dev))
     return dW, dX, colsum
-
-
-def _spmm_xw_bwd_packed(view_t, w_t, row_scale, dY, X, W, want_dx, relu_mask, row_div,
-                        win_mask, dx_out, colsum_acc, dy_colsum_out):
-    """:func:`spmm_xw_bwd`'s dX-only form gathering dY from a PackedTable."""
-    lib = L.load()
-    if X is not None or not want_dx or win_mask is not None or dy_colsum_out is not None:
-        raise ValueError("spmm_xw_bwd: a packed dY takes the dX-only form (X = None, no max)")
-    W = W.detach()
-    if W.dtype != torch.float32 or W.stride(1) != 1 or W.stride(0) % 4 or W.data_ptr() % 16:
-        W = W.to(torch.float32).contiguous()
-    dev = L.require_device(dY.words, W, view_t.rowptr, w_t, row_scale, relu_mask, row_div)
-    F_in, F_out = W.shape
-    M = view_t.n_rows
-    if dY.F != F_out:
-        raise ValueError(f"spmm_xw_bwd: packed dY of F = {dY.F}, W is [{F_in}, {F_out}]")
-    dX = dx_out if dx_out is not None else torch.empty(M, F_in, dtype=torch.float32, device=dev)
-    if (dX.dtype != torch.float32 or dX.dim() != 2 or tuple(dX.shape) != (M, F_in) or
-            dX.stride(1) != 1 or dX.stride(0) % 4 or dX.data_ptr() % 16):
-        raise ValueError(f"spmm_xw_bwd: dx_out must be float32 [{M}, {F_in}], 16-byte rows")
-    colsum = None
-    if relu_mask is not None:
-        mw = mask_words(F_in)
-        if relu_mask.shape != (M, mw) or relu_mask.dtype != torch.int32:
-            raise ValueError(f"spmm_xw_bwd: relu_mask must be int32 [{M}, {mw}]")
-        relu_mask = relu_mask.contiguous()
-        colsum = colsum_acc if colsum_acc is not None else torch.empty(F_in, dtype=torch.float32,
-                                                                         device=dev)
-    elif colsum_acc is not None:
-        raise ValueError("spmm_xw_bwd: colsum_acc needs relu_mask")
-    ws_bytes = int(lib.mgcn_spmm_xw_bwd_workspace_bytes(M, F_in, F_out))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    if _TIMER is not None:
-        _TIMER("spmm_xw_bwd_dx_pk", True, view_t.n_rows, view_t.edges)
-    pk = dY.c_struct()
-    with L.device_guard(dev):
-        rc = lib.mgcn_spmm_xw_bwd_packed(M, F_in, F_out, L.ptr(view_t.rowptr), L.ptr(view_t.col),
-                                         L.ptr(w_t), L.ptr(row_scale), L.byref(pk), L.ptr(W),
-                                         W.stride(0), L.ptr(dX), dX.stride(0), L.ptr(relu_mask),
-                                         L.ptr(row_div), L.ptr(colsum),
-                                         1 if colsum_acc is not None else 0, L.ptr(ws), ws_bytes,
-                                         L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("spmm_xw_bwd_dx_pk", False)
-    L.check(rc, "mgcn_spmm_xw_bwd_packed")
-    return None, dX, colsum
 
 
 def spmm_bwd(view_t: CSRView, w_t: torch.Tensor | None, row_scale: torch.Tensor | None,
@@ -423,492 +358,12 @@ def spmm_bwd(view_t: CSRView, w_t: torch.Tensor | None, row_scale: torch.Tensor 
     F = dY.size(1)
     dH = out if out is not None else torch.empty(view_t.n_rows, F, dtype=torch.float32,
                                                  device=dev)
-    if _TIMER is not None:
-        _TIMER("spmm_bwd", True, view_t.n_rows, view_t.edges)
-    with L.device_guard(dev):
-        rc = lib.mgcn_spmm_bwd(view_t.n_rows, F, L.ptr(view_t.rowptr), L.ptr(view_t.col),
-                               L.ptr(view_t.eid), L.ptr(w_t), L.ptr(row_scale), L.ptr(dY),
-                               dY.stride(0), L.ptr(dH), dH.stride(0), reduce, L.ptr(cnt),
-                               L.ptr(argmax), L.ptr(win_mask), L.ptr(slot_map),
-                               int(bool(accumulate)),
-                               L.ptr(view_t.order),
-                               view_t.n_heavy, view_t.n_giant, L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("spmm_bwd", False)
-    L.check(rc, "mgcn_spmm_bwd")
+    launch("spmm_bwd", "mgcn_spmm_bwd", dev, view_t.n_rows, view_t.edges, lib.mgcn_spmm_bwd,
+           view_t.n_rows, F, L.ptr(view_t.rowptr), L.ptr(view_t.col), L.ptr(view_t.eid),
+           L.ptr(w_t), L.ptr(row_scale), L.ptr(dY), dY.stride(0), L.ptr(dH), dH.stride(0), reduce,
+           L.ptr(cnt), L.ptr(argmax), L.ptr(win_mask), L.ptr(slot_map), int(bool(accumulate)),
+           L.ptr(view_t.order), view_t.n_heavy, view_t.n_giant, L.stream_of(dev))
     return dH
-
-
-def relu_bwd_colsum(dZ: torch.Tensor, Z: torch.Tensor | None, relu: bool, want_db: bool,
-                    row_div: torch.Tensor | None = None):
-    """(dY, db): dY = Z > 0 ? dZ : 0 (dZ itself when not relu), divided by
-    ``row_div`` per row when given (mean aggregation); db = sum_i of the
-    undivided dY."""
-    lib = L.load()
-    dZ = dZ.contiguous()
-    dev = L.require_device(dZ, Z, row_div)
-    n, F = dZ.shape
-    write = relu or row_div is not None
-    dY = torch.empty_like(dZ) if write else dZ
-    db = torch.empty(F, dtype=torch.float32, device=dev) if want_db else None
-    if not write and not want_db:
-        return dY, None
-    ws_bytes = int(lib.mgcn_colsum_workspace_bytes(n, F)) if want_db else 0
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev) if want_db else None
-    if _TIMER is not None:
-        _TIMER("relu_bwd_colsum", True, n)
-    with L.device_guard(dev):
-        rc = lib.mgcn_relu_bwd_colsum(n, F, L.ptr(dZ), L.ptr(Z.contiguous() if relu else None),
-                                      int(bool(relu)), L.ptr(row_div), L.ptr(dY if write else None),
-                                      L.ptr(db),
-                                      L.ptr(ws), ws_bytes, L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("relu_bwd_colsum", False)
-    L.check(rc, "mgcn_relu_bwd_colsum")
-    return dY, db
-
-
-def gemm_tn(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor | None = None,
-            accumulate: bool = False) -> torch.Tensor:
-    """C = A^T B on fp32 MFMA with split-K (libmgcn ``mgcn_gemm_tn``)."""
-    lib = L.load()
-    A = _contig_f32(A, "A")
-    B = _contig_f32(B, "B")
-    dev = L.require_device(A, B)
-    K, M = A.shape
-    if B.size(0) != K:
-        raise ValueError(f"gemm_tn: A has {K} rows, B has {B.size(0)}")
-    N = B.size(1)
-    C = out if out is not None else torch.empty(M, N, dtype=torch.float32, device=dev)
-    ws_bytes = int(lib.mgcn_gemm_tn_workspace_bytes(K, M, N))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    if _TIMER is not None:
-        _TIMER("gemm_tn", True, K)
-    with L.device_guard(dev):
-        rc = lib.mgcn_gemm_tn(K, M, N, L.ptr(A), A.stride(0), L.ptr(B), B.stride(0), L.ptr(C),
-                              C.stride(0), int(bool(accumulate)), L.ptr(ws), ws_bytes,
-                              L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("gemm_tn", False)
-    L.check(rc, "mgcn_gemm_tn")
-    return C
-
-
-def gemm_tn_split(A: torch.Tensor, B: torch.Tensor, n1: int):
-    """(C1, C2t) with A^T B = [C1 | C2t^T]: columns [0, n1) as C1 [M, n1],
-    the rest transposed as C2t [N - n1, M], both contiguous, from one
-    ``mgcn_gemm_tn_split`` pass (two parameter gradients in their own
-    layouts, no copies)."""
-    lib = L.load()
-    A = _contig_f32(A, "A")
-    B = _contig_f32(B, "B")
-    dev = L.require_device(A, B)
-    K, M = A.shape
-    N = B.size(1)
-    if B.size(0) != K or not 0 <= n1 <= N:
-        raise ValueError(f"gemm_tn_split: A {tuple(A.shape)}, B {tuple(B.shape)}, n1 {n1}")
-    C1 = torch.empty(M, n1, dtype=torch.float32, device=dev)
-    C2 = torch.empty(N - n1, M, dtype=torch.float32, device=dev)
-    ws_bytes = int(lib.mgcn_gemm_tn_workspace_bytes(K, M, N))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    if _TIMER is not None:
-        _TIMER("gemm_tn", True, K)
-    with L.device_guard(dev):
-        rc = lib.mgcn_gemm_tn_split(K, M, N, n1, L.ptr(A), A.stride(0), L.ptr(B), B.stride(0),
-                                    L.ptr(C1), max(n1, 1), L.ptr(C2), max(M, 1), 0, L.ptr(ws),
-                                    ws_bytes, L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("gemm_tn", False)
-    L.check(rc, "mgcn_gemm_tn_split")
-    return C1, C2
-
-
-def gemm_nn_supported(K: int, N: int) -> bool:
-    return bool(L.load().mgcn_gemm_nn_supported(int(K), int(N)))
-
-
-def gemm_nn_epi_supported(K: int, N: int) -> bool:
-    """The fused ReLU-mask / bias-gradient epilogue of mgcn_gemm_nn (the tuned
-    kernel, N <= 128)."""
-    return bool(L.load().mgcn_gemm_nn_epi_supported(int(K), int(N)))
-
-
-def make_relu_mask(Z: torch.Tensor) -> torch.Tensor:
-    """int32 [rows, 4]: bit b of word v set iff Z[i, 4 b + v] > 0 (F <= 128;
-    ``mgcn_relu_mask``)."""
-    lib = L.load()
-    Z = _contig_f32(Z, "Z")
-    dev = L.require_device(Z)
-    n, F = Z.shape
-    m = torch.empty(n, 4, dtype=torch.int32, device=dev)
-    with L.device_guard(dev):
-        rc = lib.mgcn_relu_mask(n, F, L.ptr(Z), Z.stride(0), L.ptr(m), L.stream_of(dev))
-    L.check(rc, "mgcn_relu_mask")
-    return m
-
-
-def gemm_nn(A: torch.Tensor, W: torch.Tensor, transpose_w: bool = False,
-            Z: torch.Tensor | None = None, row_div: torch.Tensor | None = None,
-            relu_mask: torch.Tensor | None = None):
-    """C = A @ W (or A @ W^T) on libmgcn's tall-skinny MFMA kernel
-    (``mgcn_gemm_nn``).  With ``relu_mask`` (from :func:`spmm_fwd` or
-    :func:`make_relu_mask`) or ``Z``: C = Z > 0 ? A @ W^T : 0 and the column sums
-    of C are returned too (fused ReLU backward + bias gradient).  Returns
-    (C, colsum or None)."""
-    lib = L.load()
-    A = _contig_f32(A, "A")
-    if A.stride(0) % 4 or A.data_ptr() % 16:
-        A = A.contiguous()
-    W = W.detach()
-    dev = L.require_device(A, W, Z, relu_mask)
-    if relu_mask is None and Z is not None:
-        relu_mask = make_relu_mask(Z)
-    M, K = A.shape
-    if transpose_w:
-        N, Kw = W.shape
-        sbk, sbn = W.stride(1), W.stride(0)
-    else:
-        Kw, N = W.shape
-        sbk, sbn = W.stride(0), W.stride(1)
-    if Kw != K:
-        raise ValueError(f"gemm_nn: A is [{M}, {K}], W gives K = {Kw}")
-    C = torch.empty(M, N, dtype=torch.float32, device=dev)
-    colsum = ws = None
-    ws_bytes = 0
-    if relu_mask is not None:
-        if relu_mask.shape != (M, 4) or relu_mask.dtype != torch.int32:
-            raise ValueError(f"gemm_nn: relu_mask must be int32 [{M}, 4]")
-        relu_mask = relu_mask.contiguous()
-        colsum = torch.empty(N, dtype=torch.float32, device=dev)
-        ws_bytes = int(lib.mgcn_gemm_nn_workspace_bytes(M, N))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    if _TIMER is not None:
-        _TIMER("gemm_nn", True, M)
-    with L.device_guard(dev):
-        rc = lib.mgcn_gemm_nn(M, K, N, L.ptr(A), A.stride(0), L.ptr(W), sbk, sbn, L.ptr(C),
-                              C.stride(0), L.ptr(relu_mask),
-                              L.ptr(row_div), L.ptr(colsum), L.ptr(ws), ws_bytes,
-                              L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("gemm_nn", False)
-    L.check(rc, "mgcn_gemm_nn")
-    return C, colsum
-
-
-def gemm_bwd_supported(F_in: int, F_out: int) -> bool:
-    return bool(L.load().mgcn_gemm_bwd_supported(int(F_in), int(F_out)))
-
-
-def gemm_bwd(x: torch.Tensor, dH: torch.Tensor, W: torch.Tensor, want_dx: bool = True,
-             relu_mask: torch.Tensor | None = None, row_div: torch.Tensor | None = None,
-             dW_out: torch.Tensor | None = None, accumulate: bool = False,
-             dh_colsum: bool = False):
-    """Both adjoints of H = x @ W in one pass (``mgcn_gemm_bwd``, F_in = F_out
-    = 128): dW = x^T dH and dX = dH W^T -- with ``relu_mask`` the lower
-    layer's ReLU backward and bias-gradient column sums fused as in
-    :func:`gemm_nn`.  ``dh_colsum`` (dW only): colsum = the column sums of dH
-    (a bias gradient) from the same pass.  Returns (dW, dX or None, colsum or
-    None)."""
-    lib = L.load()
-    x = _contig_f32(x, "x")
-    dH = _contig_f32(dH, "dH")
-    if x.stride(0) % 4 or x.data_ptr() % 16:
-        x = x.contiguous()
-    if dH.stride(0) % 4 or dH.data_ptr() % 16:
-        dH = dH.contiguous()
-    W = W.detach().contiguous()
-    dev = L.require_device(x, dH, W, relu_mask, row_div)
-    M, F_in = x.shape
-    F_out = dH.size(1)
-    if dH.size(0) != M or tuple(W.shape) != (F_in, F_out):
-        raise ValueError(f"gemm_bwd: x {tuple(x.shape)}, dH {tuple(dH.shape)}, W {tuple(W.shape)}")
-    dW = dW_out if dW_out is not None else torch.empty(F_in, F_out, dtype=torch.float32,
-                                                       device=dev)
-    dX = torch.empty(M, F_in, dtype=torch.float32, device=dev) if want_dx else None
-    colsum = None
-    if dh_colsum:
-        if want_dx or relu_mask is not None:
-            raise ValueError("gemm_bwd: dh_colsum is the dW-only form's")
-        colsum = torch.empty(F_out, dtype=torch.float32, device=dev)
-    if relu_mask is not None:
-        if not want_dx:
-            raise ValueError("gemm_bwd: relu_mask needs want_dx")
-        if relu_mask.shape != (M, 4) or relu_mask.dtype != torch.int32:
-            raise ValueError(f"gemm_bwd: relu_mask must be int32 [{M}, 4]")
-        relu_mask = relu_mask.contiguous()
-        colsum = torch.empty(F_in, dtype=torch.float32, device=dev)
-    ws_bytes = int(lib.mgcn_gemm_bwd_workspace_bytes(M, F_in, F_out))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    if _TIMER is not None:
-        _TIMER("gemm_bwd" if want_dx else "gemm_bwd_dw", True, M)
-    with L.device_guard(dev):
-        rc = lib.mgcn_gemm_bwd(M, F_in, F_out, L.ptr(x), x.stride(0), L.ptr(dH), dH.stride(0),
-                               L.ptr(W), W.stride(0), L.ptr(dW), dW.stride(0),
-                               int(bool(accumulate)), L.ptr(dX),
-                               dX.stride(0) if dX is not None else F_in, L.ptr(relu_mask),
-                               L.ptr(row_div), L.ptr(colsum), L.ptr(ws), ws_bytes,
-                               L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("gemm_bwd" if want_dx else "gemm_bwd_dw", False)
-    L.check(rc, "mgcn_gemm_bwd")
-    return dW, dX, colsum
-
-
-def dw_pass_supported(F_in: int, F_out: int) -> bool:
-    """The dense dW = Z^T dY pass of the reassociated backward: mgcn_gemm_bwd
-    (dW-only) at 128 x 128, mgcn_gemm_tn (bf16x6, 128 x 128 output tiles)
-    for other multiples of 128 (256 x 256: config 5)."""
-    return gemm_bwd_supported(F_in, F_out) or (int(F_in) % 128 == 0 and int(F_out) % 128 == 0)
-
-
-def dw_pass_cs(Z: torch.Tensor, dY: torch.Tensor, S: torch.Tensor):
-    """(dW = Z^T dY, the column sums of S) in one pass (``mgcn_gemm_bwd_dw_cs``,
-    128 x 128): S [M, 128] is streamed beside Z and dY -- a stack's top-layer
-    bias gradient folded into its bottom layer's dW pass."""
-    lib = L.load()
-    Z = _contig_f32(Z, "Z")
-    dY = _contig_f32(dY, "dY")
-    S = _contig_f32(S, "S")
-    for name, t in (("Z", Z), ("dY", dY), ("S", S)):
-        if t.dim() != 2 or t.size(1) != 128 or t.stride(0) % 4 or t.data_ptr() % 16:
-            raise ValueError(f"dw_pass_cs: {name} must be a [M, 128] float32 with 16-byte rows")
-    M = Z.size(0)
-    if dY.size(0) != M or S.size(0) != M:
-        raise ValueError(f"dw_pass_cs: Z, dY, S rows {M}, {dY.size(0)}, {S.size(0)}")
-    dev = L.require_device(Z, dY, S)
-    dW = torch.empty(128, 128, dtype=torch.float32, device=dev)
-    scs = torch.empty(128, dtype=torch.float32, device=dev)
-    ws_bytes = int(lib.mgcn_gemm_bwd_dw_cs_workspace_bytes(M))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    if _TIMER is not None:
-        _TIMER("gemm_bwd_dw_cs", True, M)
-    with L.device_guard(dev):
-        rc = lib.mgcn_gemm_bwd_dw_cs(M, L.ptr(Z), Z.stride(0), L.ptr(dY), dY.stride(0), L.ptr(dW),
-                                     dW.stride(0), 0, None, L.ptr(S), S.stride(0), L.ptr(scs),
-                                     L.ptr(ws), ws_bytes, L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("gemm_bwd_dw_cs", False)
-    L.check(rc, "mgcn_gemm_bwd_dw_cs")
-    return dW, scs
-
-
-def dw_pass(Z: torch.Tensor, dY: torch.Tensor, W: torch.Tensor, dh_colsum: bool = False):
-    """(dW = Z^T dY, the column sums of dY or None) -- :func:`dw_pass_supported`."""
-    if gemm_bwd_supported(W.size(0), W.size(1)):
-        dW, _, cs = gemm_bwd(Z, dY, W, want_dx=False, dh_colsum=dh_colsum)
-        return dW, cs
-    dW = gemm_tn(Z, dY)
-    cs = relu_bwd_colsum(dY, None, False, True)[1] if dh_colsum else None
-    return dW, cs
-
-
-SMALL_K = 8  # mgcn_gemm_small_k: K <= 8, N <= 128
-
-
-def gemm_small_k(A: torch.Tensor, W: torch.Tensor, transpose_w: bool = False) -> torch.Tensor:
-    """A @ W (or A @ W^T) for a contraction of at most SMALL_K features
-    (``mgcn_gemm_small_k``: k-ordered fma, HBM-bound)."""
-    lib = L.load()
-    A = _contig_f32(A, "A")
-    W = W.detach().to(torch.float32)
-    dev = L.require_device(A, W)
-    K = A.size(1)
-    N = W.size(0) if transpose_w else W.size(1)
-    if (W.size(1) if transpose_w else W.size(0)) != K:
-        raise ValueError(f"gemm_small_k: A {tuple(A.shape)}, W {tuple(W.shape)}")
-    sbk, sbn = (W.stride(1), W.stride(0)) if transpose_w else (W.stride(0), W.stride(1))
-    C = torch.empty(A.size(0), N, dtype=torch.float32, device=dev)
-    with L.device_guard(dev):
-        rc = lib.mgcn_gemm_small_k(A.size(0), K, N, L.ptr(A), A.stride(0), L.ptr(W), sbk, sbn,
-                                   L.ptr(C), C.stride(0), L.stream_of(dev))
-    L.check(rc, "mgcn_gemm_small_k")
-    return C
-
-
-# Dense products that left libmgcn for torch.matmul (hipBLASLt), by shape:
-# only non-2-D or non-fp32 operands do (every 2-D fp32 shape has a libmgcn
-# kernel since ABI v15).  tests/test_host.py holds configs 2-4 to zero.
-VENDOR_GEMMS: "Counter[tuple]" = Counter()
-
-
-def mm_route(K: int, N: int, dim: int = 2, dtype=torch.float32) -> str:
-    """Which kernel takes C[M, N] = A[M, K] B[K, N]: 'nn' (mgcn_gemm_nn: the
-    tuned kernel for K in {32, 64, 128, 256}, the generic tiled one for the
-    rest), 'small_k' (mgcn_gemm_small_k: K <= SMALL_K, N <= 128, k-ordered
-    fma) or 'vendor' (torch.matmul: non-2-D / non-fp32 operands only)."""
-    if dim != 2 or dtype != torch.float32 or K < 1 or N < 1:
-        return "vendor"
-    if K <= SMALL_K and N <= 128:
-        return "small_k"
-    return "nn"
-
-
-def _mm(x: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
-    """x @ W on libmgcn (:func:`mm_route`)."""
-    route = mm_route(W.size(0), W.size(1), x.dim(), x.dtype if W.dtype == torch.float32 else None)
-    if route == "nn":
-        return gemm_nn(x, W)[0]
-    if route == "small_k":
-        return gemm_small_k(x, W)
-    VENDOR_GEMMS[("mm", tuple(x.shape), tuple(W.shape), str(x.dtype))] += 1
-    return torch.matmul(x, W.detach())
-
-
-def _mm_t(dH: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
-    """dH @ W^T on libmgcn (:func:`mm_route`)."""
-    route = mm_route(W.size(1), W.size(0), dH.dim(),
-                     dH.dtype if W.dtype == torch.float32 else None)
-    if route == "nn":
-        return gemm_nn(dH, W, transpose_w=True)[0]
-    if route == "small_k":
-        return gemm_small_k(dH, W, transpose_w=True)
-    VENDOR_GEMMS[("mm_t", tuple(dH.shape), tuple(W.shape), str(dH.dtype))] += 1
-    return torch.matmul(dH, W.detach().t())
-
-
-def _gemm_batched(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor,
-                  a_str, b_str, c_str, M: int, N: int, K: int, batch: int,
-                  accumulate: bool = False) -> None:
-    """C (+)= A B per batch through explicit (batch, row, col) element strides
-    (``mgcn_gemm_batched``)."""
-    lib = L.load()
-    dev = L.require_device(A, B, C)
-    with L.device_guard(dev):
-        rc = lib.mgcn_gemm_batched(batch, M, N, K, L.ptr(A), *a_str, L.ptr(B), *b_str, L.ptr(C),
-                                   *c_str, 1 if accumulate else 0, L.stream_of(dev))
-    L.check(rc, "mgcn_gemm_batched")
-
-
-def _bstr(t: torch.Tensor):
-    """(batch, row, col) strides of a 3-D tensor or a broadcast 2-D one."""
-    return (t.stride(0), t.stride(1), t.stride(2)) if t.dim() == 3 else (0, t.stride(0), t.stride(1))
-
-
-class _Bmm(torch.autograd.Function):
-    """a [B, M, K] @ b ([B, K, N] or a broadcast [K, N]) on mgcn_gemm_batched,
-    with its adjoints dA = dC b^T, db = a^T dC (summed over the batch for a
-    broadcast b) through transposed strides -- no copies."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        Bn, M, K = a.shape
-        N = b.shape[-1]
-        out = torch.empty(Bn, M, N, dtype=torch.float32, device=a.device)
-        _gemm_batched(a, b, out, _bstr(a), _bstr(b), _bstr(out), M, N, K, Bn)
-        ctx.save_for_backward(a, b)
-        return out
-
-    @staticmethod
-    def backward(ctx, dC):
-        a, b = ctx.saved_tensors
-        dC = dC.to(torch.float32)  # any strides: the kernel addresses them
-        Bn, M, K = a.shape
-        N = b.shape[-1]
-        da = db = None
-        if ctx.needs_input_grad[0]:
-            da = torch.empty_like(a, memory_format=torch.contiguous_format)
-            sb = _bstr(b)
-            _gemm_batched(dC, b, da, _bstr(dC), (sb[0], sb[2], sb[1]), _bstr(da), M, K, N, Bn)
-        if ctx.needs_input_grad[1]:
-            sa = _bstr(a)
-            if b.dim() == 3:
-                db = torch.empty(Bn, K, N, dtype=torch.float32, device=a.device)
-                _gemm_batched(a, dC, db, (sa[0], sa[2], sa[1]), _bstr(dC), _bstr(db), K, N, M, Bn)
-            else:  # broadcast weight: one product over the flattened batch rows
-                a2 = a.reshape(Bn * M, K)
-                d2 = dC.reshape(Bn * M, N)
-                db = torch.empty(K, N, dtype=torch.float32, device=a.device)
-                _gemm_batched(a2, d2, db, (0, a2.stride(1), a2.stride(0)), (0, d2.stride(0),
-                              d2.stride(1)), (0, db.stride(0), db.stride(1)), K, N, Bn * M, 1)
-        return da, db
-
-
-def bmm(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """Batched dense product of DiffPool's dense operators (PyG 1.3
-    DenseSAGEConv / dense_diff_pool; reference kernel/diff_pool.py:13-14, 68,
-    76): a [B, M, K] @ b [B, K, N] (or a [K, N] weight broadcast over the
-    batch) on libmgcn's MFMA kernel, differentiable in both operands."""
-    if a.dtype != torch.float32 or b.dtype != torch.float32:
-        raise TypeError(f"bmm: float32 operands (the reference computes in fp32), got "
-                        f"{a.dtype} @ {b.dtype}")
-    if a.dim() != 3 or b.dim() not in (2, 3) or a.size(2) != b.size(-2) or \
-            (b.dim() == 3 and b.size(0) != a.size(0)):
-        raise ValueError(f"bmm: shapes {tuple(a.shape)} @ {tuple(b.shape)}")
-    L.require_device(a, b)
-    return _Bmm.apply(a, b)
-
-
-class _Linear(torch.autograd.Function):
-    """H = x @ W (gcn_base_models.py:201) with all three products on libmgcn's
-    MFMA kernels: forward on mgcn_gemm_nn (tall-skinny); backward dW = x^T dH
-    (a K = num_nodes reduction) and dX = dH W^T together in one pass of
-    mgcn_gemm_bwd at F = 128, else mgcn_gemm_tn (split-K) + mgcn_gemm_nn."""
-
-    @staticmethod
-    def forward(ctx, x, W):
-        ctx.save_for_backward(x, W)
-        return _mm(x, W)
-
-    @staticmethod
-    def backward(ctx, dH):
-        x, W = ctx.saved_tensors
-        dx = dW = None
-        dH = dH.contiguous()
-        if ctx.needs_input_grad[1] and gemm_bwd_supported(W.size(0), W.size(1)):
-            dW, dx, _ = gemm_bwd(x, dH, W, want_dx=bool(ctx.needs_input_grad[0]))
-            return dx, dW
-        if ctx.needs_input_grad[0]:
-            dx = _mm_t(dH, W)
-        if ctx.needs_input_grad[1]:
-            dW = gemm_tn(x, dH)
-        return dx, dW
-
-
-class _LinearBias(torch.autograd.Function):
-    """torch.nn.functional.linear(x, W, b) = x W^T + b with W [out, in] on the
-    libmgcn GEMMs (dW = dy^T x is the K = num_nodes reduction that hipBLASLt
-    runs at ~18 TFLOP/s: GCNModel's residual and final Linear layers,
-    gcn_model.py:64-73)."""
-
-    @staticmethod
-    def forward(ctx, x, W, b):
-        ctx.save_for_backward(x, W)
-        ctx.has_b = b is not None
-        y = _mm_t(x, W)
-        return y.add_(b.detach()) if b is not None else y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, W = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = dW = db = None
-        if ctx.needs_input_grad[0]:
-            dx = _mm(dy, W)
-        if ctx.needs_input_grad[1]:
-            dW = gemm_tn(dy, x)
-        if ctx.has_b and ctx.needs_input_grad[2]:
-            db = relu_bwd_colsum(dy, None, False, True)[1]
-        return dx, dW, db
-
-
-def linear_bias(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None) -> torch.Tensor:
-    """F.linear on libmgcn for 2-D fp32 inputs (other ranks / dtypes: torch's
-    F.linear on the same HIP device).  CPU tensors raise: no CPU path."""
-    L.require_device(x, W, b)
-    if x.dim() != 2 or x.dtype != torch.float32:
-        VENDOR_GEMMS[("linear", tuple(x.shape), tuple(W.shape), str(x.dtype))] += 1
-        return torch.nn.functional.linear(x, W, b)
-    return _LinearBias.apply(x, W, b)
-
-
-def linear(x: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
-    """``torch.matmul(x, W)`` with the libmgcn weight-gradient kernel.  CPU
-    tensors raise: no CPU path."""
-    L.require_device(x, W)
-    if x.dim() != 2 or x.dtype != torch.float32 or W.dtype != torch.float32:
-        VENDOR_GEMMS[("matmul", tuple(x.shape), tuple(W.shape), str(x.dtype))] += 1
-        return torch.matmul(x, W)
-    return _Linear.apply(x, W)
 
 
 def max_mask(plan: GraphPlan, argmax: torch.Tensor) -> torch.Tensor:
@@ -919,10 +374,9 @@ def max_mask(plan: GraphPlan, argmax: torch.Tensor) -> torch.Tensor:
     W = (F + 31) // 32
     dev = argmax.device
     mask = torch.empty(max(plan.nnz, 1), W, dtype=torch.int32, device=dev)
-    with L.device_guard(dev):
-        rc = lib.mgcn_max_mask(plan.fwd.n_rows, F, L.ptr(plan.fwd.rowptr), L.ptr(plan.fwd.eid),
-                               L.ptr(argmax), L.ptr(mask), L.stream_of(dev))
-    L.check(rc, "mgcn_max_mask")
+    launch(None, "mgcn_max_mask", dev, None, None, lib.mgcn_max_mask,
+           plan.fwd.n_rows, F, L.ptr(plan.fwd.rowptr), L.ptr(plan.fwd.eid), L.ptr(argmax),
+           L.ptr(mask), L.stream_of(dev))
     return mask
 
 
@@ -994,11 +448,9 @@ def edge_weight_grad(view: CSRView, H: torch.Tensor, dY: torch.Tensor,
         raise ValueError(f"edge_weight_grad: H {tuple(H.shape)}, dY {tuple(dY.shape)} do not fit "
                          f"the view ({view.n_rows} rows, {view.n_cols} columns)")
     dw = torch.empty(view.nnz, dtype=torch.float32, device=dev)
-    with L.device_guard(dev):
-        rc = lib.mgcn_edge_weight_grad(view.n_rows, F, L.ptr(view.rowptr), L.ptr(view.col),
-                                       L.ptr(H), H.stride(0), L.ptr(dY), dY.stride(0),
-                                       L.ptr(win_mask), L.ptr(dw), L.stream_of(dev))
-    L.check(rc, "mgcn_edge_weight_grad")
+    launch(None, "mgcn_edge_weight_grad", dev, None, None, lib.mgcn_edge_weight_grad,
+           view.n_rows, F, L.ptr(view.rowptr), L.ptr(view.col), L.ptr(H), H.stride(0), L.ptr(dY),
+           dY.stride(0), L.ptr(win_mask), L.ptr(dw), L.stream_of(dev))
     return dw
 
 
@@ -1438,10 +890,9 @@ def residual_act(Z1: torch.Tensor, R: torch.Tensor, rbias: torch.Tensor | None,
     n, F = Z1.shape
     Z = torch.empty(n, F, dtype=torch.float32, device=dev)
     rb = rbias.detach().contiguous() if rbias is not None else None
-    with L.device_guard(dev):
-        rc = lib.mgcn_residual_act(n, F, L.ptr(Z1), Z1.stride(0), L.ptr(R), R.stride(0), L.ptr(rb),
-                                   int(bool(relu)), L.ptr(Z), Z.stride(0), L.stream_of(dev))
-    L.check(rc, "mgcn_residual_act")
+    launch(None, "mgcn_residual_act", dev, None, None, lib.mgcn_residual_act,
+           n, F, L.ptr(Z1), Z1.stride(0), L.ptr(R), R.stride(0), L.ptr(rb), int(bool(relu)),
+           L.ptr(Z), Z.stride(0), L.stream_of(dev))
     return Z
 
 
@@ -1452,16 +903,14 @@ def residual_act_bwd(dZ, Z, relu, Z1, relu1, dA, dS, row_div=None, want_sums=Tru
     dev = L.require_device(dZ, dA)
     n, F = dZ.shape
     sums = torch.empty(2 * F, dtype=torch.float32, device=dev) if want_sums else None
-    ws_bytes = int(lib.mgcn_residual_act_bwd_workspace_bytes(n, F)) if want_sums else 0
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev) if want_sums else None
-    with L.device_guard(dev):
-        rc = lib.mgcn_residual_act_bwd(
-            n, F, L.ptr(dZ), dZ.stride(0), L.ptr(Z), Z.stride(0) if Z is not None else F,
-            int(bool(relu)), L.ptr(Z1), Z1.stride(0) if Z1 is not None else F, int(bool(relu1)),
-            L.ptr(row_div), L.ptr(dA), dA.stride(0), L.ptr(dS),
-            dS.stride(0) if dS is not None else F, L.ptr(sums), L.ptr(ws), ws_bytes,
-            L.stream_of(dev))
-    L.check(rc, "mgcn_residual_act_bwd")
+    ws, ws_bytes = (workspace(lib.mgcn_residual_act_bwd_workspace_bytes(n, F), dev)
+                    if want_sums else (None, 0))
+    launch(None, "mgcn_residual_act_bwd", dev, None, None, lib.mgcn_residual_act_bwd,
+           n, F, L.ptr(dZ), dZ.stride(0), L.ptr(Z), Z.stride(0) if Z is not None else F,
+           int(bool(relu)), L.ptr(Z1), Z1.stride(0) if Z1 is not None else F, int(bool(relu1)),
+           L.ptr(row_div), L.ptr(dA), dA.stride(0), L.ptr(dS),
+           dS.stride(0) if dS is not None else F, L.ptr(sums), L.ptr(ws), ws_bytes,
+           L.stream_of(dev))
     return sums
 
 
@@ -1515,14 +964,6 @@ class _ResidualGCNLayer(torch.autograd.Function):
         return (dx, None, None, None, None, None, dW, db, dWr, dbr)
 
 
-def _aligned_rows(t: torch.Tensor) -> torch.Tensor:
-    """Contiguous fp32 with 16-byte aligned rows (the fused kernels' float4 accesses)."""
-    t = _contig_f32(t, "x")
-    if t.stride(0) % 4 or t.data_ptr() % 16 or t.stride(1) != 1:
-        t = t.contiguous()
-    return t
-
-
 def residual_layer_supported(plan: GraphPlan, x: torch.Tensor, W: torch.Tensor, Wr: torch.Tensor,
                              reduce: int) -> bool:
     """True when :class:`_ResidualLayerFused` takes this layer: 32 -> 32 with a
@@ -1557,18 +998,12 @@ class _ResidualLayerFused(torch.autograd.Function):
         Z = torch.empty(n, F, dtype=torch.float32, device=dev)
         masks = torch.empty(n, 2, dtype=torch.int32, device=dev)
         v = plan.fwd
-        if _TIMER is not None:
-            _TIMER("residual_layer_fwd", True, v.n_rows, v.edges)
-        with L.device_guard(dev):
-            rc = lib.mgcn_residual_layer_fwd(n, F, L.ptr(v.rowptr), L.ptr(v.col), L.ptr(v.eid),
-                                             L.ptr(norm.w_fwd), L.ptr(x), x.stride(0), L.ptr(Wd),
-                                             F, L.ptr(bd), L.ptr(Wrd), F, L.ptr(brd), int(reduce),
-                                             int(bool(relu1)), int(bool(relu2)), L.ptr(Z), F,
-                                             L.ptr(masks), L.ptr(v.order), v.n_heavy, v.n_giant,
-                                             L.stream_of(dev))
-        if _TIMER is not None:
-            _TIMER("residual_layer_fwd", False)
-        L.check(rc, "mgcn_residual_layer_fwd")
+        launch("residual_layer_fwd", "mgcn_residual_layer_fwd", dev, v.n_rows, v.edges,
+               lib.mgcn_residual_layer_fwd,
+               n, F, L.ptr(v.rowptr), L.ptr(v.col), L.ptr(v.eid), L.ptr(norm.w_fwd), L.ptr(x),
+               x.stride(0), L.ptr(Wd), F, L.ptr(bd), L.ptr(Wrd), F, L.ptr(brd), int(reduce),
+               int(bool(relu1)), int(bool(relu2)), L.ptr(Z), F, L.ptr(masks), L.ptr(v.order),
+               v.n_heavy, v.n_giant, L.stream_of(dev))
         ctx.plan, ctx.norm, ctx.reduce, ctx.relu1, ctx.relu2 = plan, norm, reduce, relu1, relu2
         ctx.has_b, ctx.has_br = b is not None, br is not None
         ctx.save_for_backward(x, Wd, Wrd, masks)
@@ -1585,24 +1020,16 @@ class _ResidualLayerFused(torch.autograd.Function):
         dX = torch.empty(n, F, dtype=torch.float32, device=dev)
         DH = torch.empty(n, 2 * F, dtype=torch.float32, device=dev)
         sums = torch.empty(2 * F, dtype=torch.float32, device=dev)
-        ws_bytes = int(lib.mgcn_residual_layer_bwd_workspace_bytes(n, F))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        ws, ws_bytes = workspace(lib.mgcn_residual_layer_bwd_workspace_bytes(n, F), dev)
         v = plan.bwd
         rd = plan.in_cnt if ctx.reduce == L.REDUCE_MEAN else None
-        if _TIMER is not None:
-            _TIMER("residual_layer_bwd", True, v.n_rows, v.edges)
-        with L.device_guard(dev):
-            rc = lib.mgcn_residual_layer_bwd(n, F, L.ptr(v.rowptr), L.ptr(v.col), L.ptr(v.eid),
-                                             L.ptr(norm.w_bwd), L.ptr(norm.row_scale_bwd),
-                                             L.ptr(rd), L.ptr(dZ), dZ.stride(0), L.ptr(masks),
-                                             int(bool(ctx.relu1)), int(bool(ctx.relu2)),
-                                             L.ptr(Wd), F, L.ptr(Wrd), F, L.ptr(dX), F,
-                                             L.ptr(DH), 2 * F, L.ptr(sums), L.ptr(v.order),
-                                             v.n_heavy, v.n_giant, L.ptr(ws), ws_bytes,
-                                             L.stream_of(dev))
-        if _TIMER is not None:
-            _TIMER("residual_layer_bwd", False)
-        L.check(rc, "mgcn_residual_layer_bwd")
+        launch("residual_layer_bwd", "mgcn_residual_layer_bwd", dev, v.n_rows, v.edges,
+               lib.mgcn_residual_layer_bwd,
+               n, F, L.ptr(v.rowptr), L.ptr(v.col), L.ptr(v.eid), L.ptr(norm.w_bwd),
+               L.ptr(norm.row_scale_bwd), L.ptr(rd), L.ptr(dZ), dZ.stride(0), L.ptr(masks),
+               int(bool(ctx.relu1)), int(bool(ctx.relu2)), L.ptr(Wd), F, L.ptr(Wrd), F, L.ptr(dX),
+               F, L.ptr(DH), 2 * F, L.ptr(sums), L.ptr(v.order), v.n_heavy, v.n_giant, L.ptr(ws),
+               ws_bytes, L.stream_of(dev))
         # [dW | dWr^T] = x^T [dH | dS] in one pass, dWr written transposed
         dW, dWr = gemm_tn_split(x, DH, F)
         db = sums[:F] if ctx.has_b else None
@@ -1659,17 +1086,11 @@ class _ResidualStack(torch.autograd.Function):
         pr1, ar1 = _int_array(relu1s)
         pr2, ar2 = _int_array(relu2s)
         v = plan.fwd
-        if _TIMER is not None:
-            _TIMER("residual_stack_fwd", True, v.n_rows, v.edges)
-        with L.device_guard(dev):
-            rc = lib.mgcn_residual_stack_fwd(n, F, nl, L.ptr(v.rowptr), L.ptr(v.col), L.ptr(v.eid),
-                                             L.ptr(norm.w_fwd), L.ptr(x0), x0.stride(0), pw, pb,
-                                             pwr, pbr, int(reduce), pr1, pr2, L.ptr(Z),
-                                             L.ptr(masks), L.ptr(v.order), v.n_heavy, v.n_giant,
-                                             L.stream_of(dev))
-        if _TIMER is not None:
-            _TIMER("residual_stack_fwd", False)
-        L.check(rc, "mgcn_residual_stack_fwd")
+        launch("residual_stack_fwd", "mgcn_residual_stack_fwd", dev, v.n_rows, v.edges,
+               lib.mgcn_residual_stack_fwd,
+               n, F, nl, L.ptr(v.rowptr), L.ptr(v.col), L.ptr(v.eid), L.ptr(norm.w_fwd), L.ptr(x0),
+               x0.stride(0), pw, pb, pwr, pbr, int(reduce), pr1, pr2, L.ptr(Z), L.ptr(masks),
+               L.ptr(v.order), v.n_heavy, v.n_giant, L.stream_of(dev))
         ctx.plan, ctx.norm, ctx.reduce = plan, norm, reduce
         ctx.relu1s, ctx.relu2s = relu1s, relu2s
         ctx.has_b = [b is not None for b in bs]
@@ -1692,8 +1113,7 @@ class _ResidualStack(torch.autograd.Function):
         sums = torch.empty(nl, 2 * F, dtype=torch.float32, device=dev)
         dX0 = torch.empty(n, F, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] \
             else None
-        ws_bytes = int(lib.mgcn_residual_stack_bwd_workspace_bytes(n, F))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        ws, ws_bytes = workspace(lib.mgcn_residual_stack_bwd_workspace_bytes(n, F), dev)
         pw, aw = _ptr_array(Ws)
         pwr, awr = _ptr_array(Wrs)
         pdw, adw = _ptr_array([G[l, 0] for l in range(nl)])
@@ -1702,19 +1122,13 @@ class _ResidualStack(torch.autograd.Function):
         pr2, ar2 = _int_array(ctx.relu2s)
         v = plan.bwd
         rd = plan.in_cnt if ctx.reduce == L.REDUCE_MEAN else None
-        if _TIMER is not None:
-            _TIMER("residual_stack_bwd", True, v.n_rows, v.edges)
-        with L.device_guard(dev):
-            rc = lib.mgcn_residual_stack_bwd(n, F, nl, L.ptr(v.rowptr), L.ptr(v.col), L.ptr(v.eid),
-                                             L.ptr(norm.w_bwd), L.ptr(norm.row_scale_bwd),
-                                             L.ptr(rd), L.ptr(dZ), dZ.stride(0), L.ptr(x0),
-                                             x0.stride(0), L.ptr(Z), L.ptr(masks), pr1, pr2, pw,
-                                             pwr, L.ptr(dX0), pdw, pdwr, L.ptr(sums),
-                                             L.ptr(v.order), v.n_heavy, v.n_giant, L.ptr(ws),
-                                             ws_bytes, L.stream_of(dev))
-        if _TIMER is not None:
-            _TIMER("residual_stack_bwd", False)
-        L.check(rc, "mgcn_residual_stack_bwd")
+        launch("residual_stack_bwd", "mgcn_residual_stack_bwd", dev, v.n_rows, v.edges,
+               lib.mgcn_residual_stack_bwd,
+               n, F, nl, L.ptr(v.rowptr), L.ptr(v.col), L.ptr(v.eid), L.ptr(norm.w_bwd),
+               L.ptr(norm.row_scale_bwd), L.ptr(rd), L.ptr(dZ), dZ.stride(0), L.ptr(x0),
+               x0.stride(0), L.ptr(Z), L.ptr(masks), pr1, pr2, pw, pwr, L.ptr(dX0), pdw, pdwr,
+               L.ptr(sums), L.ptr(v.order), v.n_heavy, v.n_giant, L.ptr(ws), ws_bytes,
+               L.stream_of(dev))
         grads = []
         for l in range(nl):
             grads += [G[l, 0], sums[l, :F] if ctx.has_b[l] else None, G[l, 1],
@@ -1769,15 +1183,9 @@ class _InputLayer(torch.autograd.Function):
         bd = b.detach().contiguous() if b is not None else None
         brd = br.detach().contiguous() if br is not None else None
         Z = torch.empty(n, F, dtype=torch.float32, device=dev)
-        if _TIMER is not None:
-            _TIMER("input_layer_fwd", True, n)
-        with L.device_guard(dev):
-            rc = lib.mgcn_input_layer_fwd(n, F, L.ptr(a), L.ptr(x), L.ptr(Wd), L.ptr(bd),
-                                          L.ptr(Wrd), L.ptr(brd), int(relu1), int(relu2),
-                                          L.ptr(Z), Z.stride(0), L.stream_of(dev))
-        if _TIMER is not None:
-            _TIMER("input_layer_fwd", False)
-        L.check(rc, "mgcn_input_layer_fwd")
+        launch("input_layer_fwd", "mgcn_input_layer_fwd", dev, n, None, lib.mgcn_input_layer_fwd,
+               n, F, L.ptr(a), L.ptr(x), L.ptr(Wd), L.ptr(bd), L.ptr(Wrd), L.ptr(brd), int(relu1),
+               int(relu2), L.ptr(Z), Z.stride(0), L.stream_of(dev))
         ctx.plan, ctx.norm, ctx.reduce, ctx.relu1, ctx.relu2 = plan, norm, reduce, relu1, relu2
         ctx.has_b, ctx.has_br = b is not None, br is not None
         ctx.save_for_backward(x, a, Z, Wd, bd if bd is not None else torch.empty(0), Wrd)
@@ -1796,19 +1204,12 @@ class _InputLayer(torch.autograd.Function):
         dxr = torch.empty(n, dtype=torch.float32, device=dev) if need_x else None
         grads = torch.empty(4 * F, dtype=torch.float32, device=dev)
         mean = ctx.reduce == L.REDUCE_MEAN
-        ws_bytes = int(lib.mgcn_input_layer_bwd_workspace_bytes(n, F))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        if _TIMER is not None:
-            _TIMER("input_layer_bwd", True, n)
-        with L.device_guard(dev):
-            rc = lib.mgcn_input_layer_bwd(
-                n, F, L.ptr(dZ), dZ.stride(0), L.ptr(Z), Z.stride(0), L.ptr(a), L.ptr(x),
-                L.ptr(W), L.ptr(b if b.numel() else None), L.ptr(Wr), int(ctx.relu1),
-                int(ctx.relu2), L.ptr(plan.in_cnt if (mean and need_x) else None), L.ptr(da),
-                L.ptr(dxr), L.ptr(grads), L.ptr(ws), ws_bytes, L.stream_of(dev))
-        if _TIMER is not None:
-            _TIMER("input_layer_bwd", False)
-        L.check(rc, "mgcn_input_layer_bwd")
+        ws, ws_bytes = workspace(lib.mgcn_input_layer_bwd_workspace_bytes(n, F), dev)
+        launch("input_layer_bwd", "mgcn_input_layer_bwd", dev, n, None, lib.mgcn_input_layer_bwd,
+               n, F, L.ptr(dZ), dZ.stride(0), L.ptr(Z), Z.stride(0), L.ptr(a), L.ptr(x), L.ptr(W),
+               L.ptr(b if b.numel() else None), L.ptr(Wr), int(ctx.relu1), int(ctx.relu2),
+               L.ptr(plan.in_cnt if (mean and need_x) else None), L.ptr(da), L.ptr(dxr),
+               L.ptr(grads), L.ptr(ws), ws_bytes, L.stream_of(dev))
         dx = None
         if need_x:
             dx = spmm_bwd(plan.bwd, norm.w_bwd, norm.row_scale_bwd, da.view(n, 1), L.REDUCE_SUM)
@@ -1832,393 +1233,6 @@ def residual_gcn_layer(x, plan: GraphPlan, norm: NormPlan, aggr: str, relu1: boo
         return _ResidualLayerFused.apply(x, plan, norm, reduce, bool(relu1), bool(relu2), W, b,
                                          Wr, br)
     return _ResidualGCNLayer.apply(x, plan, norm, reduce, bool(relu1), bool(relu2), W, b, Wr, br)
-
-
-# --------------------------------------------------------------- attention
-def _att_call(name: str, view: CSRView | None, rows: int, fn) -> None:
-    """One libmgcn attention launch, bracketed by the kernel timer."""
-    if _TIMER is not None:
-        _TIMER(name, True, rows, view.edges if view is not None else None)
-    rc = fn()
-    if _TIMER is not None:
-        _TIMER(name, False)
-    L.check(rc, "mgcn_" + name)
-
-
-class _AttentionAggregate(torch.autograd.Function):
-    """The message passing of NodeModelAttention after its ``x @ W``
-    (graph_attention.py:66-100) on libmgcn's attention kernels.
-
-    Forward: mgcn_att_scores, then for 'in' one mgcn_att_fwd launch (logits,
-    softmax by destination, weighted gather); for 'out' mgcn_edge_softmax over
-    the source-grouped view, alpha carried to fwd slot order, mgcn_att_fwd in
-    its aggregate-only mode.  Saved: Hp, alpha (fwd slot order, before the
-    dropout mask), the slot-order mask, s_src / s_dst.  Backward:
-    mgcn_att_bwd_dst, mgcn_att_bwd_src (+ mgcn_att_dst_fold for 'out'), and the
-    attention vector's gradient as one mgcn_gemm_tn ([ds_src | ds_dst]^T Hp,
-    of which head h's own C columns are its rows of da)."""
-
-    @staticmethod
-    def forward(ctx, Hp, att, mask, plan: GraphPlan, H: int, act: int, att_dir: str):
-        lib = L.load()
-        dev = Hp.device
-        N, HC = Hp.shape
-        C = HC // H
-        nnz = plan.nnz
-        st = L.stream_of(dev)
-        att = att.detach().contiguous()
-        s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        Y = torch.empty(N, HC, dtype=torch.float32, device=dev)
-        alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-        fwd, bwd = plan.fwd, plan.bwd
-        with L.device_guard(dev):
-            _att_call("att_scores", None, N, lambda: lib.mgcn_att_scores(
-                N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st))
-            if att_dir == 'in' or nnz == 0:
-                _att_call("att_fwd", fwd, N, lambda: lib.mgcn_att_fwd(
-                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst), L.ptr(s_src),
-                    act, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, L.ptr(alpha),
-                    st))
-            else:
-                a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-                _att_call("edge_softmax", bwd, N, lambda: lib.mgcn_edge_softmax(
-                    N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
-                    L.ptr(a_bwd), st))
-                alpha[plan.slot_map()[:nnz].long()] = a_bwd
-                _att_call("att_fwd", fwd, N, lambda: lib.mgcn_att_fwd(
-                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act,
-                    L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None, st))
-        ctx.plan, ctx.H, ctx.act, ctx.att_dir = plan, H, act, att_dir
-        ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
-        ctx.mark_non_differentiable(alpha)
-        return Y, alpha
-
-    @staticmethod
-    def backward(ctx, dY, _dalpha):
-        Hp, att, alpha, mask, s_src, s_dst = ctx.saved_tensors
-        plan, H, act = ctx.plan, ctx.H, ctx.act
-        lib = L.load()
-        dev = Hp.device
-        N, HC = Hp.shape
-        C = HC // H
-        nnz = plan.nnz
-        st = L.stream_of(dev)
-        dY = _contig_f32(dY, "dY")
-        fwd, bwd = plan.fwd, plan.bwd
-        slot = plan.slot_map() if nnz else None
-        dz = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-        ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        dHp = torch.empty(N, HC, dtype=torch.float32, device=dev)
-        inn = ctx.att_dir == 'in'
-        with L.device_guard(dev):
-            _att_call("att_bwd_dst", fwd, N, lambda: lib.mgcn_att_bwd_dst(
-                N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
-                L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst), L.ptr(s_src),
-                act, int(inn), L.ptr(dz), L.ptr(ds_dst), st))
-            _att_call("att_bwd_src", bwd, N, lambda: lib.mgcn_att_bwd_src(
-                N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
-                dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
-                act, int(not inn), L.ptr(att), L.ptr(ds_dst) if inn else None, L.ptr(ds_src),
-                L.ptr(dHp), HC, st))
-            if not inn:
-                _att_call("att_dst_fold", fwd, N, lambda: lib.mgcn_att_dst_fold(
-                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(dz), L.ptr(att), L.ptr(ds_dst),
-                    L.ptr(dHp), HC, st))
-        datt = None
-        if ctx.needs_input_grad[1]:
-            full = gemm_tn(torch.cat([ds_src, ds_dst], dim=1), Hp)
-            full = full.view(2, H, H, C)  # [src | dst, head of ds, head of Hp, c]
-            hh = torch.arange(H, device=dev)
-            datt = torch.cat([full[0, hh, hh], full[1, hh, hh]], dim=1)  # [H, 2C]
-        return dHp, datt, None, None, None, None, None
-
-
-def attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphPlan, nheads: int,
-                        act: str = 'none', att_dir: str = 'in',
-                        edge_mask: torch.Tensor | None = None):
-    """Multi-head soft attention over each node's neighbourhood
-    (graph_attention.py:66-100 + the softmax of common.py:69-92), fused:
-
-    ``Hp`` [N, H * C] (or [N, H, C]) are the transformed features, ``att_weight``
-    [1, H, 2C] (or [H, 2C]) the attention vector, ``act`` in none / lrelu /
-    relu, ``att_dir`` 'in' (softmax over the edges into a node) or 'out' (over
-    the edges out of it).  ``edge_mask`` [E, H], in COO edge order, multiplies
-    the attention coefficients (the dropout mask with its 1 / (1 - p) scale).
-
-    Returns ``(Y, alpha_coo)``: Y [N, H * C] = sum over in-edges of alpha' *
-    Hp[src], and alpha' = alpha * mask as [E, H] in COO order, detached.
-    Differentiable in Hp and att_weight.  CPU tensors raise: no CPU path."""
-    L.require_device(Hp, att_weight, plan.fwd.rowptr, edge_mask)
-    if act not in L.ATT_ACT_CODES:
-        raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
-    if att_dir not in ('in', 'out'):
-        raise ValueError(f"att_dir must be 'in' or 'out', got {att_dir!r}")
-    H = int(nheads)
-    Hp2 = _contig_f32(Hp.reshape(Hp.size(0), -1), "Hp")
-    if Hp2.size(0) != plan.num_nodes:
-        raise ValueError(f"Hp has {Hp2.size(0)} rows, graph has {plan.num_nodes} nodes")
-    HC = Hp2.size(1)
-    if H < 1 or HC % H:
-        raise ValueError(f"Hp width {HC} is not a multiple of nheads = {H}")
-    C = HC // H
-    if att_weight.dtype != torch.float32 or att_weight.numel() != 2 * HC:
-        raise ValueError(f"att_weight must be float32 [1, {H}, {2 * C}], got "
-                         f"{att_weight.dtype} {tuple(att_weight.shape)}")
-    if not (1 <= H <= 16 and HC <= 1024 and plan.nnz * H < 2 ** 31):
-        raise L.MgcnError(f"attention_aggregate: unsupported shape (H = {H}, C = {C}, nnz = "
-                          f"{plan.nnz}): need 1 <= H <= 16, H C <= 1024, nnz H < 2^31")
-    mask = None
-    if edge_mask is not None:
-        if tuple(edge_mask.shape) != (plan.nnz, H):
-            raise ValueError(f"edge_mask must be [{plan.nnz}, {H}] in COO order, got "
-                             f"{tuple(edge_mask.shape)}")
-        mask = edge_mask.detach().to(torch.float32)[plan.fwd.eid.long()].contiguous()
-    Y, alpha = _AttentionAggregate.apply(Hp2, att_weight.reshape(H, 2 * C), mask, plan, H,
-                                         L.ATT_ACT_CODES[act], att_dir)
-    alpha = alpha.detach()
-    alpha_coo = torch.empty_like(alpha)
-    if plan.nnz:
-        alpha_coo[plan.fwd.eid.long()] = alpha * mask if mask is not None else alpha
-    return Y, alpha_coo
-
-
-# ---------------------------------------------------------- hard attention
-class _HardAttentionTrain(torch.autograd.Function):
-    """The training branch of NodeModelHardAttention / VotePoolLayer after
-    ``x @ W`` (graph_hard_attention.py:82-103): soft attention whose logit is
-    (act(z) + noise) / T, on the mgcn_hatt_* instantiations of the attention
-    kernels.  Launches, saved tensors and the backward are those of
-    :class:`_AttentionAggregate` (the noise is not saved: act' needs z alone);
-    ``noise`` is in the slot order of the view the softmax walks."""
-
-    @staticmethod
-    def forward(ctx, Hp, att, mask, noise, plan: GraphPlan, H: int, act: int, att_dir: str,
-                T: float):
-        lib = L.load()
-        dev = Hp.device
-        N, HC = Hp.shape
-        C = HC // H
-        nnz = plan.nnz
-        st = L.stream_of(dev)
-        att = att.detach().contiguous()
-        s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        Y = torch.empty(N, HC, dtype=torch.float32, device=dev)
-        alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-        fwd, bwd = plan.fwd, plan.bwd
-        with L.device_guard(dev):
-            _att_call("att_scores", None, N, lambda: lib.mgcn_att_scores(
-                N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st))
-            if att_dir == 'in' or nnz == 0:
-                _att_call("hatt_fwd", fwd, N, lambda: lib.mgcn_hatt_fwd(
-                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst), L.ptr(s_src),
-                    act, L.ptr(noise), T, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y),
-                    HC, L.ptr(alpha), st))
-            else:
-                a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-                _att_call("hatt_edge_softmax", bwd, N, lambda: lib.mgcn_hatt_edge_softmax(
-                    N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
-                    L.ptr(noise), T, L.ptr(a_bwd), st))
-                alpha[plan.slot_map()[:nnz].long()] = a_bwd
-                _att_call("hatt_fwd", fwd, N, lambda: lib.mgcn_hatt_fwd(
-                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act, None, T,
-                    L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None, st))
-        ctx.plan, ctx.H, ctx.act, ctx.att_dir, ctx.T = plan, H, act, att_dir, T
-        ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
-        ctx.mark_non_differentiable(alpha)
-        return Y, alpha
-
-    @staticmethod
-    def backward(ctx, dY, _dalpha):
-        Hp, att, alpha, mask, s_src, s_dst = ctx.saved_tensors
-        plan, H, act, T = ctx.plan, ctx.H, ctx.act, ctx.T
-        lib = L.load()
-        dev = Hp.device
-        N, HC = Hp.shape
-        C = HC // H
-        nnz = plan.nnz
-        st = L.stream_of(dev)
-        dY = _contig_f32(dY, "dY")
-        fwd, bwd = plan.fwd, plan.bwd
-        slot = plan.slot_map() if nnz else None
-        dz = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-        ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        dHp = torch.empty(N, HC, dtype=torch.float32, device=dev)
-        inn = ctx.att_dir == 'in'
-        with L.device_guard(dev):
-            _att_call("hatt_bwd_dst", fwd, N, lambda: lib.mgcn_hatt_bwd_dst(
-                N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
-                L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst), L.ptr(s_src),
-                act, int(inn), T, L.ptr(dz), L.ptr(ds_dst), st))
-            _att_call("hatt_bwd_src", bwd, N, lambda: lib.mgcn_hatt_bwd_src(
-                N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
-                dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
-                act, int(not inn), T, L.ptr(att), L.ptr(ds_dst) if inn else None, L.ptr(ds_src),
-                L.ptr(dHp), HC, st))
-            if not inn:
-                _att_call("att_dst_fold", fwd, N, lambda: lib.mgcn_att_dst_fold(
-                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(dz), L.ptr(att), L.ptr(ds_dst),
-                    L.ptr(dHp), HC, st))
-        datt = None
-        if ctx.needs_input_grad[1]:
-            full = gemm_tn(torch.cat([ds_src, ds_dst], dim=1), Hp)
-            full = full.view(2, H, H, C)  # [src | dst, head of ds, head of Hp, c]
-            hh = torch.arange(H, device=dev)
-            datt = torch.cat([full[0, hh, hh], full[1, hh, hh]], dim=1)  # [H, 2C]
-        return dHp, datt, None, None, None, None, None, None, None
-
-
-class _HardAttentionEval(torch.autograd.Function):
-    """The eval branch (graph_hard_attention.py:105-139): per-(group, head)
-    argmax, the reference's one-hot including its last-edge quirk, and the
-    gather that reads one row per winner.
-
-    Forward: mgcn_att_scores, mgcn_hatt_select over the view whose rows are the
-    softmax groups ('out': the bwd view, the one-hot carried to fwd slot order
-    through the slot map), the quirk on the one-hot, mgcn_hatt_gather.  Saved:
-    the one-hot (fwd slot order) and the attention vector (only as the
-    finite multiplier of a zero ds).  Backward: dHp[j] = sum_k alpha_k dY[i]
-    through mgcn_att_bwd_src with a zero dz; nothing flows to att_weight."""
-
-    @staticmethod
-    def forward(ctx, Hp, att, noise, plan: GraphPlan, H: int, act: int, att_dir: str):
-        lib = L.load()
-        dev = Hp.device
-        N, HC = Hp.shape
-        C = HC // H
-        nnz = plan.nnz
-        st = L.stream_of(dev)
-        att = att.detach().contiguous()
-        s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        Y = torch.empty(N, HC, dtype=torch.float32, device=dev)
-        alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-        winner = torch.empty(N, H, dtype=torch.int32, device=dev)
-        fwd, bwd = plan.fwd, plan.bwd
-        with L.device_guard(dev):
-            _att_call("att_scores", None, N, lambda: lib.mgcn_att_scores(
-                N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st))
-            if att_dir == 'in':
-                _att_call("hatt_select", fwd, N, lambda: lib.mgcn_hatt_select(
-                    N, nnz, H, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst), L.ptr(s_src), act,
-                    L.ptr(noise), L.ptr(alpha), L.ptr(winner), st))
-            else:
-                a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-                _att_call("hatt_select", bwd, N, lambda: lib.mgcn_hatt_select(
-                    N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
-                    L.ptr(noise), L.ptr(a_bwd), L.ptr(winner), st))
-                if nnz:
-                    alpha[plan.slot_map()[:nnz].long()] = a_bwd
-            if nnz:
-                # graph_hard_attention.py:118-123: an argmax of -1 (a group without a
-                # winner) indexes the transposed flat one-hot at E h - 1, which is COO
-                # edge E - 1 of head h - 1 (head 0: of the last head)
-                mark = (winner < 0).any(dim=0).roll(-1).to(torch.float32)
-                last = plan.last_edge_slot()  # cached on the plan: no scan, no host sync
-                alpha[last] = torch.maximum(alpha[last], mark)
-            _att_call("hatt_gather", fwd, N, lambda: lib.mgcn_hatt_gather(
-                N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(alpha), L.ptr(Hp),
-                Hp.stride(0), L.ptr(Y), HC, st))
-        ctx.plan, ctx.H = plan, H
-        ctx.save_for_backward(alpha, att)
-        ctx.mark_non_differentiable(alpha)
-        return Y, alpha
-
-    @staticmethod
-    def backward(ctx, dY, _dalpha):
-        alpha, att = ctx.saved_tensors
-        plan, H = ctx.plan, ctx.H
-        lib = L.load()
-        dev = alpha.device
-        N, nnz = plan.num_nodes, plan.nnz
-        dY = _contig_f32(dY, "dY")
-        HC = dY.size(1)
-        bwd = plan.bwd
-        slot = plan.slot_map() if nnz else None
-        dz = torch.zeros(nnz, H, dtype=torch.float32, device=dev)
-        ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        dHp = torch.empty(N, HC, dtype=torch.float32, device=dev)
-        with L.device_guard(dev):
-            _att_call("att_bwd_src", bwd, N, lambda: lib.mgcn_att_bwd_src(
-                N, nnz, H, HC // H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
-                dY.stride(0), L.ptr(alpha), None, L.ptr(dz), None, None, 0, 0, L.ptr(att), None,
-                L.ptr(ds_src), L.ptr(dHp), HC, L.stream_of(dev)))
-        return dHp, None, None, None, None, None, None
-
-
-def hard_attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphPlan,
-                             nheads: int, act: str = 'none', att_dir: str = 'in',
-                             temperature: float = 0.1, *, training: bool,
-                             noise: torch.Tensor | None = None,
-                             edge_mask: torch.Tensor | None = None):
-    """Multi-head hard attention over each node's neighbourhood
-    (graph_hard_attention.py:82-139), fused.  Arguments as for
-    :func:`attention_aggregate`, plus:
-
-    ``training=True``: Gumbel-softmax.  The logit of an edge is
-    ``(act(z) + noise) / temperature``; ``noise`` [E, H] in COO edge order
-    (None: zeros).  Differentiable in Hp and att_weight.
-
-    ``training=False``: every (group, head) keeps the one edge with the largest
-    ``act(z) + noise`` (``noise`` None: the plain argmax; given: the reference's
-    ``sample=True``), ties going to the last edge in COO order.  If any group
-    has no winner, COO edge E - 1 is selected too (on every head when the group
-    is empty), as the reference's flat indexing with argmax = -1 does.
-    Differentiable in Hp only; ``att_weight`` receives no gradient and
-    ``edge_mask`` is not used (the reference drops out in training alone).
-
-    Returns ``(Y, alpha_coo)``: Y [N, H * C] and the coefficients that weighted
-    the messages, [E, H] in COO order, detached."""
-    L.require_device(Hp, att_weight, plan.fwd.rowptr, edge_mask, noise)
-    if act not in L.ATT_ACT_CODES:
-        raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
-    if att_dir not in ('in', 'out'):
-        raise ValueError(f"att_dir must be 'in' or 'out', got {att_dir!r}")
-    H = int(nheads)
-    Hp2 = _contig_f32(Hp.reshape(Hp.size(0), -1), "Hp")
-    if Hp2.size(0) != plan.num_nodes:
-        raise ValueError(f"Hp has {Hp2.size(0)} rows, graph has {plan.num_nodes} nodes")
-    HC = Hp2.size(1)
-    if H < 1 or HC % H:
-        raise ValueError(f"Hp width {HC} is not a multiple of nheads = {H}")
-    C = HC // H
-    if att_weight.dtype != torch.float32 or att_weight.numel() != 2 * HC:
-        raise ValueError(f"att_weight must be float32 [1, {H}, {2 * C}], got "
-                         f"{att_weight.dtype} {tuple(att_weight.shape)}")
-    if not (1 <= H <= 16 and HC <= 1024 and plan.nnz * H < 2 ** 31):
-        raise L.MgcnError(f"hard_attention_aggregate: unsupported shape (H = {H}, C = {C}, nnz = "
-                          f"{plan.nnz}): need 1 <= H <= 16, H C <= 1024, nnz H < 2^31")
-    T = float(temperature)
-    if training and not T > 0:
-        raise ValueError(f"temperature must be positive, got {temperature!r}")
-    # the view whose rows are the softmax / argmax groups
-    walked = plan.fwd if att_dir == 'in' or (training and plan.nnz == 0) else plan.bwd
-    if noise is not None:
-        if tuple(noise.shape) != (plan.nnz, H):
-            raise ValueError(f"noise must be [{plan.nnz}, {H}] in COO order, got "
-                             f"{tuple(noise.shape)}")
-        noise = noise.detach().to(torch.float32)[walked.eid.long()].contiguous()
-    att2 = att_weight.reshape(H, 2 * C)
-    mask = None
-    if training:
-        if edge_mask is not None:
-            if tuple(edge_mask.shape) != (plan.nnz, H):
-                raise ValueError(f"edge_mask must be [{plan.nnz}, {H}] in COO order, got "
-                                 f"{tuple(edge_mask.shape)}")
-            mask = edge_mask.detach().to(torch.float32)[plan.fwd.eid.long()].contiguous()
-        Y, alpha = _HardAttentionTrain.apply(Hp2, att2, mask, noise, plan, H,
-                                             L.ATT_ACT_CODES[act], att_dir, T)
-    else:
-        Y, alpha = _HardAttentionEval.apply(Hp2, att2.detach(), noise, plan, H,
-                                            L.ATT_ACT_CODES[act], att_dir)
-    alpha = alpha.detach()
-    alpha_coo = torch.empty_like(alpha)
-    if plan.nnz:
-        alpha_coo[plan.fwd.eid.long()] = alpha * mask if mask is not None else alpha
-    return Y, alpha_coo
 
 
 # ---------------------------------------------------------------- scatter_
@@ -2270,186 +1284,3 @@ def scatter_(name: str, src: torch.Tensor, index: torch.Tensor, dim_size: int | 
     x = src.unsqueeze(1) if squeeze else src
     y = _SegmentReduce.apply(x, index, int(dim_size), L.REDUCE_CODES[name])
     return y.squeeze(1) if squeeze else y
-
-
-def segment_mean(x: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
-    """Mean of contiguous row segments [ptr[g], ptr[g+1]) (global_mean_pool)."""
-    return _SegmentMean.apply(x, ptr)
-
-
-class _SegmentMean(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, ptr):
-        lib = L.load()
-        x = _contig_f32(x, "x")
-        ptr = ptr.to(torch.int64).contiguous()
-        dev = L.require_device(x, ptr)
-        G = ptr.numel() - 1
-        out = torch.empty(G, x.size(1), dtype=torch.float32, device=dev)
-        with L.device_guard(dev):
-            rc = lib.mgcn_segment_mean(G, x.size(1), L.ptr(ptr), L.ptr(x), x.stride(0), L.ptr(out),
-                                       out.stride(0), L.stream_of(dev))
-        L.check(rc, "mgcn_segment_mean")
-        ctx.save_for_backward(ptr)
-        ctx.n = x.size(0)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        (ptr,) = ctx.saved_tensors
-        counts = (ptr[1:] - ptr[:-1])
-        seg = torch.repeat_interleave(torch.arange(counts.numel(), device=ptr.device), counts,
-                                      output_size=ctx.n)
-        scale = counts.clamp(min=1).to(dout.dtype)
-        return (dout / scale.unsqueeze(1))[seg], None
-
-
-# ------------------------------------------------- packed table exchange
-def pack_rows_count(rows: torch.Tensor, hdr: torch.Tensor, counts: torch.Tensor) -> None:
-    """hdr[i, 2 w] = mask word w of rows[i] (its not-+0.0 bits), counts[i] =
-    their number (``mgcn_pack_rows_count``; mgcn.dist's packed exchange).
-    ``hdr`` is the [n, 2 F/32] int32 header of the packed chunk."""
-    lib = L.load()
-    rows = _contig_f32(rows, "rows")
-    n, F = rows.shape
-    dev = L.require_device(rows, hdr, counts)
-    if hdr.shape != (n, 2 * (F // 32)) or hdr.dtype != torch.int32 or not hdr.is_contiguous() \
-            or counts.shape != (n,) or counts.dtype != torch.int32:
-        raise ValueError("pack_rows_count: hdr int32 [n, 2 F/32] contiguous, counts int32 [n]")
-    if _TIMER is not None:
-        _TIMER("pack_rows_count", True, n)
-    with L.device_guard(dev):
-        rc = lib.mgcn_pack_rows_count(n, F, L.ptr(rows), rows.stride(0), L.ptr(hdr),
-                                      L.ptr(counts), L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("pack_rows_count", False)
-    L.check(rc, "mgcn_pack_rows_count")
-
-
-def pack_rows_values(rows: torch.Tensor, offs: torch.Tensor, hdr: torch.Tensor,
-                     vals: torch.Tensor) -> None:
-    """vals[offs[i] ...] = the not-+0.0 words of rows[i] in order, and the
-    header's value positions hdr[i, 2 w + 1] (``mgcn_pack_rows_values``)."""
-    lib = L.load()
-    rows = _contig_f32(rows, "rows")
-    n, F = rows.shape
-    dev = L.require_device(rows, offs, hdr, vals)
-    if offs.shape != (n,) or offs.dtype != torch.int32 or vals.dtype != torch.int32 or \
-            hdr.shape != (n, 2 * (F // 32)) or hdr.dtype != torch.int32 or not hdr.is_contiguous():
-        raise ValueError("pack_rows_values: offs int32 [n], hdr int32 [n, 2 F/32], vals int32")
-    if _TIMER is not None:
-        _TIMER("pack_rows_values", True, n)
-    with L.device_guard(dev):
-        rc = lib.mgcn_pack_rows_values(n, F, L.ptr(rows), rows.stride(0), L.ptr(offs),
-                                       L.ptr(hdr), L.ptr(vals), L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("pack_rows_values", False)
-    L.check(rc, "mgcn_pack_rows_values")
-
-
-@dataclass
-class PackedTable:
-    """An exchange table as the zero-skipping exchange delivered it
-    (``mgcn_packed_table``): C x P packed segments of ``seg_rows`` rows each
-    (pack.hip's layout), segment s at word ``seg_off[s]`` of buffer
-    ``bufs[seg_buf[s]]`` (one receive buffer per row chunk, or one for all).
-    The fused 128- and 256-wide layer kernels gather from it in place
-    (:func:`spmm_xw_fwd` / :func:`spmm_xw_bwd` with a PackedTable for X / dY,
-    over a view whose columns are packed positions (s << row_bits) | i:
-    :func:`packed_cols`).  At F = 128 every segment must lie within 2 GiB of
-    the lowest buffer (the kernels read the table through one range: in
-    practice, one buffer)."""
-    bufs: list               # int32 tensors holding the segments (kept alive here)
-    seg_buf: list            # segment s -> index into bufs
-    seg_off: list            # segment s -> word offset in that buffer
-    seg_rows: int
-    row_bits: int
-    F: int
-
-    @property
-    def n_seg(self) -> int:
-        return len(self.seg_off)
-
-    @property
-    def words(self) -> torch.Tensor:
-        return self.bufs[0]
-
-    def c_struct(self):
-        """The C descriptor: every segment's offset counted from the lowest
-        buffer address (one device address space)."""
-        if self.n_seg > 64:
-            raise ValueError(f"PackedTable: {self.n_seg} segments (at most 64)")
-        ptrs = [b.data_ptr() for b in self.bufs]
-        anchor = min(ptrs)
-        if any((p - anchor) % 4 for p in ptrs):
-            raise ValueError("PackedTable: buffers must be 4-byte aligned")
-        rel = [(p - anchor) // 4 for p in ptrs]
-        t = L.PackedTableC()
-        t.words = anchor
-        t.n_words = max(r + b.numel() for r, b in zip(rel, self.bufs))
-        t.n_seg = self.n_seg
-        t.seg_rows = int(self.seg_rows)
-        t.row_bits = int(self.row_bits)
-        t.F = int(self.F)
-        for s_, (bi, off) in enumerate(zip(self.seg_buf, self.seg_off)):
-            t.seg_base[s_] = rel[bi] + int(off)
-        return t
-
-
-def packed_row_bits(seg_rows: int) -> int:
-    return max(int(seg_rows - 1).bit_length(), 0)
-
-
-def packed_cols(col: torch.Tensor, seg_rows: int, row_bits: int) -> torch.Tensor:
-    """Table positions t (row t % seg_rows of segment t // seg_rows) ->
-    packed positions (s << row_bits) | i, int32."""
-    t = col.to(torch.int64)
-    s_ = torch.div(t, seg_rows, rounding_mode="floor")
-    return ((s_ << row_bits) | (t - s_ * seg_rows)).to(torch.int32)
-
-
-PACK_ROWS_WIDTHS = (32, 64, 128, 256)  # mgcn_pack_rows: one 256-word segment per row
-
-
-def pack_rows(rows: torch.Tensor, hdr: torch.Tensor, vals: torch.Tensor,
-              total: torch.Tensor) -> None:
-    """The packed chunk in one pass (``mgcn_pack_rows``): hdr as
-    pack_rows_count + pack_rows_values write it, vals, and total[0] = the
-    number of values (device int64) -- no counts, no scan."""
-    lib = L.load()
-    rows = _contig_f32(rows, "rows")
-    n, F = rows.shape
-    dev = L.require_device(rows, hdr, vals, total)
-    if F not in PACK_ROWS_WIDTHS or hdr.shape != (n, 2 * (F // 32)) or hdr.dtype != torch.int32 \
-            or not hdr.is_contiguous() or vals.dtype != torch.int32 or total.dtype != torch.int64 \
-            or total.numel() < 1:
-        raise ValueError("pack_rows: F in (32, 64, 128, 256), hdr int32 [n, 2 F/32] contiguous, "
-                         "vals int32, total int64")
-    ws_bytes = int(lib.mgcn_pack_rows_workspace_bytes(n, F))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    if _TIMER is not None:
-        _TIMER("pack_rows", True, n)
-    with L.device_guard(dev):
-        rc = lib.mgcn_pack_rows(n, F, L.ptr(rows), rows.stride(0), L.ptr(hdr), L.ptr(vals),
-                                L.ptr(total), L.ptr(ws), ws_bytes, L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("pack_rows", False)
-    L.check(rc, "mgcn_pack_rows")
-
-
-def unpack_rows(buf: torch.Tensor, n_seg: int, n: int, seg_words: int, out: torch.Tensor) -> None:
-    """out[p n + i] = row i of packed segment p of ``buf`` (``mgcn_unpack_rows``)."""
-    lib = L.load()
-    dev = L.require_device(buf, out)
-    F = out.size(1)
-    if buf.dtype != torch.int32 or not buf.is_contiguous() or buf.numel() < n_seg * seg_words or \
-            out.dtype != torch.float32 or out.size(0) < n_seg * n or out.stride(1) != 1:
-        raise ValueError("unpack_rows: buf int32 [n_seg * seg_words], out float32 [n_seg * n, F]")
-    if _TIMER is not None:
-        _TIMER("unpack_rows", True, n_seg * n)
-    with L.device_guard(dev):
-        rc = lib.mgcn_unpack_rows(n_seg, n, F, L.ptr(buf), seg_words, L.ptr(out), out.stride(0),
-                                  L.stream_of(dev))
-    if _TIMER is not None:
-        _TIMER("unpack_rows", False)
-    L.check(rc, "mgcn_unpack_rows")

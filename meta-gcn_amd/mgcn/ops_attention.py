@@ -1,0 +1,381 @@
+"""Soft and hard multi-head attention over a graph plan on libmgcn's
+attention kernels.  Sits on :mod:`mgcn.ops_gemm` (the attention vector's
+gradient is one ``gemm_tn``); :mod:`mgcn.ops` re-exports every name."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib as L
+from ._call import _contig_f32, launch
+from .graph import GraphPlan
+from .ops_gemm import gemm_tn
+
+
+class _AttentionAggregate(torch.autograd.Function):
+    """The message passing of NodeModelAttention after its ``x @ W``
+    (graph_attention.py:66-100) on libmgcn's attention kernels.
+
+    Forward: mgcn_att_scores, then for 'in' one mgcn_att_fwd launch (logits,
+    softmax by destination, weighted gather); for 'out' mgcn_edge_softmax over
+    the source-grouped view, alpha carried to fwd slot order, mgcn_att_fwd in
+    its aggregate-only mode.  Saved: Hp, alpha (fwd slot order, before the
+    dropout mask), the slot-order mask, s_src / s_dst.  Backward:
+    mgcn_att_bwd_dst, mgcn_att_bwd_src (+ mgcn_att_dst_fold for 'out'), and the
+    attention vector's gradient as one mgcn_gemm_tn ([ds_src | ds_dst]^T Hp,
+    of which head h's own C columns are its rows of da)."""
+
+    @staticmethod
+    def forward(ctx, Hp, att, mask, plan: GraphPlan, H: int, act: int, att_dir: str):
+        lib = L.load()
+        dev = Hp.device
+        N, HC = Hp.shape
+        C = HC // H
+        nnz = plan.nnz
+        st = L.stream_of(dev)
+        att = att.detach().contiguous()
+        s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+        s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
+        Y = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+        fwd, bwd = plan.fwd, plan.bwd
+        launch("att_scores", "mgcn_att_scores", dev, N, None, lib.mgcn_att_scores,
+               N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
+        if att_dir == 'in' or nnz == 0:
+            launch("att_fwd", "mgcn_att_fwd", dev, N, fwd.edges, lib.mgcn_att_fwd,
+                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst), L.ptr(s_src),
+                   act, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, L.ptr(alpha), st)
+        else:
+            a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+            launch("edge_softmax", "mgcn_edge_softmax", dev, N, bwd.edges, lib.mgcn_edge_softmax,
+                   N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
+                   L.ptr(a_bwd), st)
+            alpha[plan.slot_map()[:nnz].long()] = a_bwd
+            launch("att_fwd", "mgcn_att_fwd", dev, N, fwd.edges, lib.mgcn_att_fwd,
+                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act,
+                   L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None, st)
+        ctx.plan, ctx.H, ctx.act, ctx.att_dir = plan, H, act, att_dir
+        ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
+        ctx.mark_non_differentiable(alpha)
+        return Y, alpha
+
+    @staticmethod
+    def backward(ctx, dY, _dalpha):
+        Hp, att, alpha, mask, s_src, s_dst = ctx.saved_tensors
+        plan, H, act = ctx.plan, ctx.H, ctx.act
+        lib = L.load()
+        dev = Hp.device
+        N, HC = Hp.shape
+        C = HC // H
+        nnz = plan.nnz
+        st = L.stream_of(dev)
+        dY = _contig_f32(dY, "dY")
+        fwd, bwd = plan.fwd, plan.bwd
+        slot = plan.slot_map() if nnz else None
+        dz = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+        ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+        ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
+        dHp = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        inn = ctx.att_dir == 'in'
+        launch("att_bwd_dst", "mgcn_att_bwd_dst", dev, N, fwd.edges, lib.mgcn_att_bwd_dst,
+               N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
+               L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst), L.ptr(s_src),
+               act, int(inn), L.ptr(dz), L.ptr(ds_dst), st)
+        launch("att_bwd_src", "mgcn_att_bwd_src", dev, N, bwd.edges, lib.mgcn_att_bwd_src,
+               N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
+               dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
+               act, int(not inn), L.ptr(att), L.ptr(ds_dst) if inn else None, L.ptr(ds_src),
+               L.ptr(dHp), HC, st)
+        if not inn:
+            launch("att_dst_fold", "mgcn_att_dst_fold", dev, N, fwd.edges, lib.mgcn_att_dst_fold,
+                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(dz), L.ptr(att), L.ptr(ds_dst),
+                   L.ptr(dHp), HC, st)
+        datt = None
+        if ctx.needs_input_grad[1]:
+            full = gemm_tn(torch.cat([ds_src, ds_dst], dim=1), Hp)
+            full = full.view(2, H, H, C)  # [src | dst, head of ds, head of Hp, c]
+            hh = torch.arange(H, device=dev)
+            datt = torch.cat([full[0, hh, hh], full[1, hh, hh]], dim=1)  # [H, 2C]
+        return dHp, datt, None, None, None, None, None
+
+
+def attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphPlan, nheads: int,
+                        act: str = 'none', att_dir: str = 'in',
+                        edge_mask: torch.Tensor | None = None):
+    """Multi-head soft attention over each node's neighbourhood
+    (graph_attention.py:66-100 + the softmax of common.py:69-92), fused:
+
+    ``Hp`` [N, H * C] (or [N, H, C]) are the transformed features, ``att_weight``
+    [1, H, 2C] (or [H, 2C]) the attention vector, ``act`` in none / lrelu /
+    relu, ``att_dir`` 'in' (softmax over the edges into a node) or 'out' (over
+    the edges out of it).  ``edge_mask`` [E, H], in COO edge order, multiplies
+    the attention coefficients (the dropout mask with its 1 / (1 - p) scale).
+
+    Returns ``(Y, alpha_coo)``: Y [N, H * C] = sum over in-edges of alpha' *
+    Hp[src], and alpha' = alpha * mask as [E, H] in COO order, detached.
+    Differentiable in Hp and att_weight.  CPU tensors raise: no CPU path."""
+    L.require_device(Hp, att_weight, plan.fwd.rowptr, edge_mask)
+    if act not in L.ATT_ACT_CODES:
+        raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
+    if att_dir not in ('in', 'out'):
+        raise ValueError(f"att_dir must be 'in' or 'out', got {att_dir!r}")
+    H = int(nheads)
+    Hp2 = _contig_f32(Hp.reshape(Hp.size(0), -1), "Hp")
+    if Hp2.size(0) != plan.num_nodes:
+        raise ValueError(f"Hp has {Hp2.size(0)} rows, graph has {plan.num_nodes} nodes")
+    HC = Hp2.size(1)
+    if H < 1 or HC % H:
+        raise ValueError(f"Hp width {HC} is not a multiple of nheads = {H}")
+    C = HC // H
+    if att_weight.dtype != torch.float32 or att_weight.numel() != 2 * HC:
+        raise ValueError(f"att_weight must be float32 [1, {H}, {2 * C}], got "
+                         f"{att_weight.dtype} {tuple(att_weight.shape)}")
+    if not (1 <= H <= 16 and HC <= 1024 and plan.nnz * H < 2 ** 31):
+        raise L.MgcnError(f"attention_aggregate: unsupported shape (H = {H}, C = {C}, nnz = "
+                          f"{plan.nnz}): need 1 <= H <= 16, H C <= 1024, nnz H < 2^31")
+    mask = None
+    if edge_mask is not None:
+        if tuple(edge_mask.shape) != (plan.nnz, H):
+            raise ValueError(f"edge_mask must be [{plan.nnz}, {H}] in COO order, got "
+                             f"{tuple(edge_mask.shape)}")
+        mask = edge_mask.detach().to(torch.float32)[plan.fwd.eid.long()].contiguous()
+    Y, alpha = _AttentionAggregate.apply(Hp2, att_weight.reshape(H, 2 * C), mask, plan, H,
+                                         L.ATT_ACT_CODES[act], att_dir)
+    alpha = alpha.detach()
+    alpha_coo = torch.empty_like(alpha)
+    if plan.nnz:
+        alpha_coo[plan.fwd.eid.long()] = alpha * mask if mask is not None else alpha
+    return Y, alpha_coo
+
+
+# ---------------------------------------------------------- hard attention
+class _HardAttentionTrain(torch.autograd.Function):
+    """The training branch of NodeModelHardAttention / VotePoolLayer after
+    ``x @ W`` (graph_hard_attention.py:82-103): soft attention whose logit is
+    (act(z) + noise) / T, on the mgcn_hatt_* instantiations of the attention
+    kernels.  Launches, saved tensors and the backward are those of
+    :class:`_AttentionAggregate` (the noise is not saved: act' needs z alone);
+    ``noise`` is in the slot order of the view the softmax walks."""
+
+    @staticmethod
+    def forward(ctx, Hp, att, mask, noise, plan: GraphPlan, H: int, act: int, att_dir: str,
+                T: float):
+        lib = L.load()
+        dev = Hp.device
+        N, HC = Hp.shape
+        C = HC // H
+        nnz = plan.nnz
+        st = L.stream_of(dev)
+        att = att.detach().contiguous()
+        s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+        s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
+        Y = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+        fwd, bwd = plan.fwd, plan.bwd
+        launch("att_scores", "mgcn_att_scores", dev, N, None, lib.mgcn_att_scores,
+               N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
+        if att_dir == 'in' or nnz == 0:
+            launch("hatt_fwd", "mgcn_hatt_fwd", dev, N, fwd.edges, lib.mgcn_hatt_fwd,
+                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst), L.ptr(s_src),
+                   act, L.ptr(noise), T, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y),
+                   HC, L.ptr(alpha), st)
+        else:
+            a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+            launch("hatt_edge_softmax", "mgcn_hatt_edge_softmax", dev, N, bwd.edges,
+                   lib.mgcn_hatt_edge_softmax,
+                   N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
+                   L.ptr(noise), T, L.ptr(a_bwd), st)
+            alpha[plan.slot_map()[:nnz].long()] = a_bwd
+            launch("hatt_fwd", "mgcn_hatt_fwd", dev, N, fwd.edges, lib.mgcn_hatt_fwd,
+                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act, None, T,
+                   L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None, st)
+        ctx.plan, ctx.H, ctx.act, ctx.att_dir, ctx.T = plan, H, act, att_dir, T
+        ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
+        ctx.mark_non_differentiable(alpha)
+        return Y, alpha
+
+    @staticmethod
+    def backward(ctx, dY, _dalpha):
+        Hp, att, alpha, mask, s_src, s_dst = ctx.saved_tensors
+        plan, H, act, T = ctx.plan, ctx.H, ctx.act, ctx.T
+        lib = L.load()
+        dev = Hp.device
+        N, HC = Hp.shape
+        C = HC // H
+        nnz = plan.nnz
+        st = L.stream_of(dev)
+        dY = _contig_f32(dY, "dY")
+        fwd, bwd = plan.fwd, plan.bwd
+        slot = plan.slot_map() if nnz else None
+        dz = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+        ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+        ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
+        dHp = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        inn = ctx.att_dir == 'in'
+        launch("hatt_bwd_dst", "mgcn_hatt_bwd_dst", dev, N, fwd.edges, lib.mgcn_hatt_bwd_dst,
+               N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
+               L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst), L.ptr(s_src),
+               act, int(inn), T, L.ptr(dz), L.ptr(ds_dst), st)
+        launch("hatt_bwd_src", "mgcn_hatt_bwd_src", dev, N, bwd.edges, lib.mgcn_hatt_bwd_src,
+               N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
+               dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
+               act, int(not inn), T, L.ptr(att), L.ptr(ds_dst) if inn else None, L.ptr(ds_src),
+               L.ptr(dHp), HC, st)
+        if not inn:
+            launch("att_dst_fold", "mgcn_att_dst_fold", dev, N, fwd.edges, lib.mgcn_att_dst_fold,
+                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(dz), L.ptr(att), L.ptr(ds_dst),
+                   L.ptr(dHp), HC, st)
+        datt = None
+        if ctx.needs_input_grad[1]:
+            full = gemm_tn(torch.cat([ds_src, ds_dst], dim=1), Hp)
+            full = full.view(2, H, H, C)  # [src | dst, head of ds, head of Hp, c]
+            hh = torch.arange(H, device=dev)
+            datt = torch.cat([full[0, hh, hh], full[1, hh, hh]], dim=1)  # [H, 2C]
+        return dHp, datt, None, None, None, None, None, None, None
+
+
+class _HardAttentionEval(torch.autograd.Function):
+    """The eval branch (graph_hard_attention.py:105-139): per-(group, head)
+    argmax, the reference's one-hot including its last-edge quirk, and the
+    gather that reads one row per winner.
+
+    Forward: mgcn_att_scores, mgcn_hatt_select over the view whose rows are the
+    softmax groups ('out': the bwd view, the one-hot carried to fwd slot order
+    through the slot map), the quirk on the one-hot, mgcn_hatt_gather.  Saved:
+    the one-hot (fwd slot order) and the attention vector (only as the
+    finite multiplier of a zero ds).  Backward: dHp[j] = sum_k alpha_k dY[i]
+    through mgcn_att_bwd_src with a zero dz; nothing flows to att_weight."""
+
+    @staticmethod
+    def forward(ctx, Hp, att, noise, plan: GraphPlan, H: int, act: int, att_dir: str):
+        lib = L.load()
+        dev = Hp.device
+        N, HC = Hp.shape
+        C = HC // H
+        nnz = plan.nnz
+        st = L.stream_of(dev)
+        att = att.detach().contiguous()
+        s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+        s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
+        Y = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+        winner = torch.empty(N, H, dtype=torch.int32, device=dev)
+        fwd, bwd = plan.fwd, plan.bwd
+        launch("att_scores", "mgcn_att_scores", dev, N, None, lib.mgcn_att_scores,
+               N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
+        if att_dir == 'in':
+            launch("hatt_select", "mgcn_hatt_select", dev, N, fwd.edges, lib.mgcn_hatt_select,
+                   N, nnz, H, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst), L.ptr(s_src), act,
+                   L.ptr(noise), L.ptr(alpha), L.ptr(winner), st)
+        else:
+            a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+            launch("hatt_select", "mgcn_hatt_select", dev, N, bwd.edges, lib.mgcn_hatt_select,
+                   N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
+                   L.ptr(noise), L.ptr(a_bwd), L.ptr(winner), st)
+            if nnz:
+                alpha[plan.slot_map()[:nnz].long()] = a_bwd
+        if nnz:
+            # graph_hard_attention.py:118-123: an argmax of -1 (a group without a
+            # winner) indexes the transposed flat one-hot at E h - 1, which is COO
+            # edge E - 1 of head h - 1 (head 0: of the last head)
+            mark = (winner < 0).any(dim=0).roll(-1).to(torch.float32)
+            last = plan.last_edge_slot()  # cached on the plan: no scan, no host sync
+            alpha[last] = torch.maximum(alpha[last], mark)
+        launch("hatt_gather", "mgcn_hatt_gather", dev, N, fwd.edges, lib.mgcn_hatt_gather,
+               N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(alpha), L.ptr(Hp),
+               Hp.stride(0), L.ptr(Y), HC, st)
+        ctx.plan, ctx.H = plan, H
+        ctx.save_for_backward(alpha, att)
+        ctx.mark_non_differentiable(alpha)
+        return Y, alpha
+
+    @staticmethod
+    def backward(ctx, dY, _dalpha):
+        alpha, att = ctx.saved_tensors
+        plan, H = ctx.plan, ctx.H
+        lib = L.load()
+        dev = alpha.device
+        N, nnz = plan.num_nodes, plan.nnz
+        dY = _contig_f32(dY, "dY")
+        HC = dY.size(1)
+        bwd = plan.bwd
+        slot = plan.slot_map() if nnz else None
+        dz = torch.zeros(nnz, H, dtype=torch.float32, device=dev)
+        ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+        dHp = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        launch("att_bwd_src", "mgcn_att_bwd_src", dev, N, bwd.edges, lib.mgcn_att_bwd_src,
+               N, nnz, H, HC // H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
+               dY.stride(0), L.ptr(alpha), None, L.ptr(dz), None, None, 0, 0, L.ptr(att), None,
+               L.ptr(ds_src), L.ptr(dHp), HC, L.stream_of(dev))
+        return dHp, None, None, None, None, None, None
+
+
+def hard_attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphPlan,
+                             nheads: int, act: str = 'none', att_dir: str = 'in',
+                             temperature: float = 0.1, *, training: bool,
+                             noise: torch.Tensor | None = None,
+                             edge_mask: torch.Tensor | None = None):
+    """Multi-head hard attention over each node's neighbourhood
+    (graph_hard_attention.py:82-139), fused.  Arguments as for
+    :func:`attention_aggregate`, plus:
+
+    ``training=True``: Gumbel-softmax.  The logit of an edge is
+    ``(act(z) + noise) / temperature``; ``noise`` [E, H] in COO edge order
+    (None: zeros).  Differentiable in Hp and att_weight.
+
+    ``training=False``: every (group, head) keeps the one edge with the largest
+    ``act(z) + noise`` (``noise`` None: the plain argmax; given: the reference's
+    ``sample=True``), ties going to the last edge in COO order.  If any group
+    has no winner, COO edge E - 1 is selected too (on every head when the group
+    is empty), as the reference's flat indexing with argmax = -1 does.
+    Differentiable in Hp only; ``att_weight`` receives no gradient and
+    ``edge_mask`` is not used (the reference drops out in training alone).
+
+    Returns ``(Y, alpha_coo)``: Y [N, H * C] and the coefficients that weighted
+    the messages, [E, H] in COO order, detached."""
+    L.require_device(Hp, att_weight, plan.fwd.rowptr, edge_mask, noise)
+    if act not in L.ATT_ACT_CODES:
+        raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
+    if att_dir not in ('in', 'out'):
+        raise ValueError(f"att_dir must be 'in' or 'out', got {att_dir!r}")
+    H = int(nheads)
+    Hp2 = _contig_f32(Hp.reshape(Hp.size(0), -1), "Hp")
+    if Hp2.size(0) != plan.num_nodes:
+        raise ValueError(f"Hp has {Hp2.size(0)} rows, graph has {plan.num_nodes} nodes")
+    HC = Hp2.size(1)
+    if H < 1 or HC % H:
+        raise ValueError(f"Hp width {HC} is not a multiple of nheads = {H}")
+    C = HC // H
+    if att_weight.dtype != torch.float32 or att_weight.numel() != 2 * HC:
+        raise ValueError(f"att_weight must be float32 [1, {H}, {2 * C}], got "
+                         f"{att_weight.dtype} {tuple(att_weight.shape)}")
+    if not (1 <= H <= 16 and HC <= 1024 and plan.nnz * H < 2 ** 31):
+        raise L.MgcnError(f"hard_attention_aggregate: unsupported shape (H = {H}, C = {C}, nnz = "
+                          f"{plan.nnz}): need 1 <= H <= 16, H C <= 1024, nnz H < 2^31")
+    T = float(temperature)
+    if training and not T > 0:
+        raise ValueError(f"temperature must be positive, got {temperature!r}")
+    # the view whose rows are the softmax / argmax groups
+    walked = plan.fwd if att_dir == 'in' or (training and plan.nnz == 0) else plan.bwd
+    if noise is not None:
+        if tuple(noise.shape) != (plan.nnz, H):
+            raise ValueError(f"noise must be [{plan.nnz}, {H}] in COO order, got "
+                             f"{tuple(noise.shape)}")
+        noise = noise.detach().to(torch.float32)[walked.eid.long()].contiguous()
+    att2 = att_weight.reshape(H, 2 * C)
+    mask = None
+    if training:
+        if edge_mask is not None:
+            if tuple(edge_mask.shape) != (plan.nnz, H):
+                raise ValueError(f"edge_mask must be [{plan.nnz}, {H}] in COO order, got "
+                                 f"{tuple(edge_mask.shape)}")
+            mask = edge_mask.detach().to(torch.float32)[plan.fwd.eid.long()].contiguous()
+        Y, alpha = _HardAttentionTrain.apply(Hp2, att2, mask, noise, plan, H,
+                                             L.ATT_ACT_CODES[act], att_dir, T)
+    else:
+        Y, alpha = _HardAttentionEval.apply(Hp2, att2.detach(), noise, plan, H,
+                                            L.ATT_ACT_CODES[act], att_dir)
+    alpha = alpha.detach()
+    alpha_coo = torch.empty_like(alpha)
+    if plan.nnz:
+        alpha_coo[plan.fwd.eid.long()] = alpha * mask if mask is not None else alpha
+    return Y, alpha_coo
