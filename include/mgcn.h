@@ -247,6 +247,44 @@ int mgcn_spmm_bwd(int64_t n_rows, int32_t F, const int64_t *rowptr_t,
                   const int32_t *order, int64_t n_heavy, int64_t n_giant, void *stream);
 
 /*
+ * bf16 feature rows (additions to ABI 22, backward compatible).  H / Y (dY /
+ * dH) hold bf16 bit patterns, leading dimensions are counted in elements;
+ * edge weights, bias, row_scale and cnt stay fp32.  Contract: every element
+ * is widened to fp32 (exact), the row is formed exactly as mgcn_spmm_fwd /
+ * mgcn_spmm_bwd form it (same order, same roundings, fp32 accumulators), and
+ * the fp32 result is rounded once, to nearest even, at the store -- the
+ * output is bit for bit bf16(mgcn_spmm_fwd(float(H))); argmax and win_mask
+ * are the fp32 entry point's.  The adjoint's MEAN divides every gathered dY
+ * row by cnt in fp32 inside the kernel (pass the undivided dY).
+ * Shapes: F % 8 == 0 and 16-byte aligned rows (pointers % 16 == 0, leading
+ * dimensions % 8 == 0), as mgcn_spmm_bf16_supported reports; anything else is
+ * MGCN_EINVAL.  (order, n_heavy, n_giant) as above: every row, however long,
+ * is folded in edge order.
+ */
+int mgcn_spmm_bf16_supported(int32_t F, int64_t ld_in, int64_t ld_out);
+int mgcn_spmm_fwd_bf16(int64_t n_rows, int32_t F, const int64_t *rowptr,
+                       const int32_t *col, const int32_t *eid, const float *w,
+                       const uint16_t *H, int64_t ldh, uint16_t *Y, int64_t ldy,
+                       int reduce, const float *bias, int relu, int32_t *argmax,
+                       uint32_t *win_mask, const int32_t *order, int64_t n_heavy,
+                       int64_t n_giant, void *stream);
+int mgcn_spmm_bwd_bf16(int64_t n_rows, int32_t F, const int64_t *rowptr_t,
+                       const int32_t *col_t, const int32_t *eid_t, const float *w_t,
+                       const float *row_scale, const uint16_t *dY, int64_t lddy,
+                       uint16_t *dH, int64_t lddh, int reduce, const float *cnt,
+                       const int32_t *argmax, const uint32_t *win_mask,
+                       const int32_t *slot_map, const int32_t *order, int64_t n_heavy,
+                       int64_t n_giant, void *stream);
+/*
+ * dY = Z > 0 ? dZ : 0 over contiguous bf16 [n_rows, F] (exact; written only
+ * when relu != 0 and dY != NULL) and db[f] = sum_i dY[i, f] in fp32, in a
+ * fixed order (when db != NULL; workspace of mgcn_colsum_workspace_bytes).
+ */
+int mgcn_relu_bwd_colsum_bf16(int64_t n_rows, int32_t F, const uint16_t *dZ,
+                              const uint16_t *Z, int relu, uint16_t *dY, float *db,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Row schedule (degree skew: the botnet graphs reach degree ~6k, config 3).
  * mgcn_row_schedule writes every row id into order[n_rows], by degree,
  * heaviest first (stable: equal degrees keep ascending ids), and returns

@@ -136,6 +136,40 @@ __device__ __forceinline__ void store_i(int32_t *p, const I32v<V> &r) {
   }
 }
 
+// Storage of the gathered operand and of the output rows: float as it stands,
+// or bf16 bit patterns (spmm_bf16.hip) widened on load (exact) and rounded to
+// nearest even at the final store; everything between is the same fp32 code.
+template <int V>
+__device__ __forceinline__ F32v<V> load_x(const float *p) {
+  return load_f<V>(p);
+}
+template <int V>
+__device__ __forceinline__ F32v<V> load_x(const uint16_t *p) {
+  F32v<V> r;
+  if constexpr (V == 4) {
+    const uint2 t = *reinterpret_cast<const uint2 *>(p);
+    r.v[0] = __uint_as_float(t.x << 16); r.v[1] = __uint_as_float(t.x & 0xffff0000u);
+    r.v[2] = __uint_as_float(t.y << 16); r.v[3] = __uint_as_float(t.y & 0xffff0000u);
+  } else if constexpr (V == 2) {
+    const uint32_t t = *reinterpret_cast<const uint32_t *>(p);
+    r.v[0] = __uint_as_float(t << 16); r.v[1] = __uint_as_float(t & 0xffff0000u);
+  } else {
+    r.v[0] = __uint_as_float((uint32_t)*p << 16);
+  }
+  return r;
+}
+__device__ __forceinline__ float load_y(const float *p) { return *p; }
+__device__ __forceinline__ float load_y(const uint16_t *p) {
+  return __uint_as_float((uint32_t)*p << 16);
+}
+__device__ __forceinline__ void store_y(float *p, float v) { *p = v; }
+__device__ __forceinline__ void store_y(uint16_t *p, float v) {  // v_cvt_pk_bf16_f32, RNE
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+  const f2 t = {v, 0.0f};
+  *p = (uint16_t)__builtin_bit_cast(uint32_t, __builtin_convertvector(t, b2));
+}
+
 #ifdef MGCN_HEAVY_PROFILE
 // phase timestamps of workgroup 0 (scripts/prof_heavy.py): [role][batch][begin, end]
 // role 0: fold wave, 1: first producer wave, 2: last producer wave
@@ -174,8 +208,9 @@ __device__ unsigned long long g_hprof[3][256][2];
 // made the heavy kernels 3-4 us faster per launch than the same code over the
 // kernel's extern array (config 3).
 // (Q: edge quads in flight per producer thread, 0 = the kernel's choice; a
-// caller with fewer registers to spare passes a smaller one)
-template <int VEC, int MODE, int HB, int Q = 0>
+// caller with fewer registers to spare passes a smaller one; T: the storage
+// of a.X and a.Y -- float, or uint16_t for bf16 rows behind the same pointers)
+template <int VEC, int MODE, int HB, int Q = 0, typename T = float>
 __device__ __forceinline__ void heavy_row_block(const SpmmArgs &a, int FC, int BE, int64_t hidx,
                                                 float *__restrict__ smem) {
   constexpr bool kFwd = (MODE == FWD_SUM || MODE == FWD_MAX);
@@ -251,7 +286,7 @@ __device__ __forceinline__ void heavy_row_block(const SpmmArgs &a, int FC, int B
       const float *Wt = WtR(b), *Cnt = CntR(b);
       const int nb = batch_len(b);
       const int nq = (nb + 3) >> 2;
-      const float *xs = a.X + f0 + c_first * VEC;
+      const T *xs = reinterpret_cast<const T *>(a.X) + f0 + c_first * VEC;
       bool first = true;
       if (pt < npe) {
         for (int g0 = g_first; g0 < nq; g0 += kQ * dk) {
@@ -265,7 +300,7 @@ __device__ __forceinline__ void heavy_row_block(const SpmmArgs &a, int FC, int B
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 if (4 * g + e < nb) {
-                  x[u][e] = load_f<VEC>(xs + (int64_t)cols.v[e] * a.ldx);
+                  x[u][e] = load_x<VEC>(xs + (int64_t)cols.v[e] * a.ldx);
                   if constexpr (kMaxBwd) {
                     if constexpr (MODE == BWD_MAXM) {  // winner flags of this edge (1 / 0)
                       const int64_t W = (a.F + 31) >> 5;
@@ -428,7 +463,7 @@ __device__ __forceinline__ void heavy_row_block(const SpmmArgs &a, int FC, int B
     }
     if (t < fc) {
       const int f = f0 + t;
-      float *dst = a.Y + row * a.ldy + f;
+      T *dst = reinterpret_cast<T *>(a.Y) + row * a.ldy + f;
       if constexpr (kFwd) {
         float y = acc;
         if constexpr (MODE == FWD_MAX) {
@@ -442,12 +477,12 @@ __device__ __forceinline__ void heavy_row_block(const SpmmArgs &a, int FC, int B
         }
         if (a.bias != nullptr) y = __fadd_rn(y, a.bias[f]);
         if (a.relu) y = (y < 0.0f) ? 0.0f : y;
-        *dst = y;
+        store_y(dst, y);
       } else {
         float v = acc;
         if (a.row_scale != nullptr) v = __fmul_rn(v, a.row_scale[row]);
-        if (a.accumulate) v = __fadd_rn(*dst, v);
-        *dst = v;
+        if (a.accumulate) v = __fadd_rn(load_y(dst), v);
+        store_y(dst, v);
       }
     }
     if constexpr (MODE == FWD_MAX) {

@@ -490,7 +490,9 @@ class GCNStack(nn.Module):
         super().__init__()
         self.layers = nn.ModuleList(layers)
 
-    def _fusable(self):
+    def _fusable(self, x=None):
+        if x is not None and x.dtype != torch.float32:
+            return None  # bf16 activations: layer by layer (no fused bf16 layer kernel)
         nms = []
         for layer in self.layers:
             g = layer.gcn
@@ -504,7 +506,7 @@ class GCNStack(nn.Module):
         return nms
 
     def forward(self, x, edge_index, deg=None, edge_weight=None):
-        nms = self._fusable()
+        nms = self._fusable(x)
         if nms is None or x.device.type != "cuda":
             for layer in self.layers:
                 x = layer(x, edge_index, None, deg, edge_weight)
@@ -596,6 +598,8 @@ class GCNModel(nn.Module):
             return False
         if x.device.type != "cuda" or not isinstance(self.non_linear, nn.ReLU):
             return False
+        if x.dtype != torch.float32:
+            return False  # bf16 activations: step for step
         if self.training and self.dropout.p > 0:
             return False
         for layer in self.gcn_net:

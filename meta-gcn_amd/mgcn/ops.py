@@ -37,6 +37,8 @@ from .ops_gemm import (SMALL_K, VENDOR_GEMMS, _Bmm, _bstr, _gemm_batched,  # noq
 from .ops_attention import (_AttentionAggregate, _HardAttentionEval,  # noqa: F401
                             _HardAttentionTrain, attention_aggregate,
                             hard_attention_aggregate)
+from .ops_bf16 import (ROW_COPIES, _AggregateBf16, _SegmentReduceBf16,  # noqa: F401
+                       relu_bwd_colsum_bf16, spmm_bf16_supported, spmm_bwd_bf16, spmm_fwd_bf16)
 from .ops_pack import (PACK_ROWS_WIDTHS, PackedTable, _SegmentMean, pack_rows,  # noqa: F401
                        pack_rows_count, pack_rows_values, packed_cols, packed_row_bits,
                        segment_mean, unpack_rows)
@@ -411,6 +413,16 @@ class _Aggregate(torch.autograd.Function):
         return dH, db, None, None, None, None
 
 
+def _feature_dtype(t: torch.Tensor, name: str) -> bool:
+    """True for a bfloat16 feature tensor (the bf16 kernels of
+    :mod:`mgcn.ops_bf16`), False for float32; any other dtype raises."""
+    if t.dtype == torch.float32:
+        return False
+    if t.dtype == torch.bfloat16:
+        return True
+    raise TypeError(f"{name} must be float32 or bfloat16, got {t.dtype}")
+
+
 def aggregate(H: torch.Tensor, edge_index: torch.Tensor, aggr: str = "add",
               deg_norm: str | None = None, deg: torch.Tensor | None = None,
               edge_weight: torch.Tensor | None = None, bias: torch.Tensor | None = None,
@@ -426,6 +438,7 @@ def aggregate(H: torch.Tensor, edge_index: torch.Tensor, aggr: str = "add",
         raise ValueError(f"aggr must be one of add/mean/max, got {aggr!r}")
     if deg_norm not in L.NORM_CODES:
         raise ValueError(f"deg_norm must be None, 'sm' or 'rw', got {deg_norm!r}")
+    _feature_dtype(H, "H")
     n = H.size(0) if num_nodes is None else int(num_nodes)
     plan = plan_for(edge_index, n)
     norm = plan.norm(deg_norm, deg=deg, edge_weight=edge_weight)
@@ -492,7 +505,15 @@ class _AggregateW(torch.autograd.Function):
 
 def aggregate_plan(H: torch.Tensor, plan: GraphPlan, norm: NormPlan, aggr: str = "add",
                    bias: torch.Tensor | None = None, relu: bool = False) -> torch.Tensor:
-    """:func:`aggregate` on an already-built plan (no cache lookup)."""
+    """:func:`aggregate` on an already-built plan (no cache lookup).  A
+    bfloat16 ``H`` takes the bf16 kernels (:class:`_AggregateBf16`: bf16 in
+    and out, fp32 weights, bias and accumulators); a shape they do not take
+    (F % 8 != 0) or a differentiable norm goes through the fp32 path on the
+    upcast rows and is rounded once -- the same bits by the kernels' contract."""
+    if _feature_dtype(H, "H"):
+        if H.dim() == 2 and spmm_bf16_supported(H.size(1)) and not norm.grad:
+            return _AggregateBf16.apply(H, bias, plan, norm, L.REDUCE_CODES[aggr], bool(relu))
+        return aggregate_plan(H.float(), plan, norm, aggr, bias, relu).to(torch.bfloat16)
     if norm.grad:
         return _AggregateW.apply(H, norm.w_fwd, bias, plan, norm, L.REDUCE_CODES[aggr],
                                  bool(relu))
@@ -563,12 +584,17 @@ def gcn_layer(x: torch.Tensor, W: torch.Tensor, plan: GraphPlan, norm: NormPlan,
     reference uses: ``aggregate_first`` (PyG SAGEConv: mean_j x_j, then
     @ W + b) or x @ W first (the default)."""
     reduce = L.REDUCE_CODES[aggr]
+    if x.dtype == torch.bfloat16 and W.dtype != x.dtype:
+        # fp32 master weights under bf16 activations: the cast is an autograd
+        # node, so W receives an fp32 gradient; the bias stays fp32 into the
+        # aggregation's epilogue
+        W = W.to(x.dtype)
     if _FUSE_XW and not norm.grad and layer_fusable(plan, x, W, reduce):
         return _LayerXW.apply(x, W, bias, plan, norm, reduce, bool(relu))
     if aggregate_first:
         out = linear(aggregate_plan(x, plan, norm, aggr), W)
         if bias is not None:
-            out = out + bias
+            out = out + bias.to(out.dtype)
         return torch.relu(out) if relu else out
     return aggregate_plan(linear(x, W), plan, norm, aggr, bias, relu)
 
@@ -1280,6 +1306,11 @@ def scatter_(name: str, src: torch.Tensor, index: torch.Tensor, dim_size: int | 
         raise NotImplementedError("scatter_(out=...) is not supported; the reference never uses it")
     if dim_size is None:
         dim_size = int(index.max().item()) + 1 if index.numel() else 0
+    if _feature_dtype(src, "src"):
+        if src.dim() == 2 and spmm_bf16_supported(src.size(1)):
+            return _SegmentReduceBf16.apply(src, index, int(dim_size), L.REDUCE_CODES[name])
+        # 1-D src, F % 8 != 0: the fp32 path on the upcast rows, rounded once
+        return scatter_(name, src.float(), index, dim_size).to(torch.bfloat16)
     squeeze = src.dim() == 1
     x = src.unsqueeze(1) if squeeze else src
     y = _SegmentReduce.apply(x, index, int(dim_size), L.REDUCE_CODES[name])

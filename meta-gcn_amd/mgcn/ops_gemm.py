@@ -416,6 +416,11 @@ def linear_bias(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None) -> tor
     """F.linear on libmgcn for 2-D fp32 inputs (other ranks / dtypes: torch's
     F.linear on the same HIP device).  CPU tensors raise: no CPU path."""
     L.require_device(x, W, b)
+    if x.dtype == torch.bfloat16:
+        # bf16 activations: weight and bias cast through autograd (fp32
+        # master parameters receive fp32 gradients), product on the vendor GEMM
+        W = W.to(x.dtype)
+        b = b.to(x.dtype) if b is not None else None
     if x.dim() != 2 or x.dtype != torch.float32:
         VENDOR_GEMMS[("linear", tuple(x.shape), tuple(W.shape), str(x.dtype))] += 1
         return torch.nn.functional.linear(x, W, b)
@@ -426,6 +431,8 @@ def linear(x: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
     """``torch.matmul(x, W)`` with the libmgcn weight-gradient kernel.  CPU
     tensors raise: no CPU path."""
     L.require_device(x, W)
+    if x.dtype == torch.bfloat16 and W.dtype != x.dtype:
+        W = W.to(x.dtype)  # fp32 master weight: cast through autograd
     if x.dim() != 2 or x.dtype != torch.float32 or W.dtype != torch.float32:
         VENDOR_GEMMS[("matmul", tuple(x.shape), tuple(W.shape), str(x.dtype))] += 1
         return torch.matmul(x, W)
