@@ -118,6 +118,16 @@ int mgcn_check_device(void *stream, int sync);
  *                   counter in the call's workspace, so that the workgroups
  *                   end together), 0 .. 64, default 8; 0 = every chunk goes
  *                   to workgroup c mod grid.  Per-row results: same bits.
+ *                   (The warp-specialised forward, at half the grid, claims
+ *                   twice as many rounds: the same chunks.)
+ *   "xw_fwd_ws"   : 1 (default) = mgcn_spmm_xw_fwd at F = 128 on the
+ *                   warp-specialised kernel where a workspace is given (one
+ *                   workgroup per CU: 8 gather waves with the rolling gather,
+ *                   8 MFMA waves, a ring of chunk images in LDS), 0 = the
+ *                   two-phase kernel.  Same sums and products in the same
+ *                   order: Y, Z and the mask words keep their bits.  (The
+ *                   packed forward and calls without a workspace or with
+ *                   "spmm_xw_unroll" off its default are always two-phase.)
  *   "xw_ws_full"  : 1 (default) = mgcn_spmm_xw_bwd's dW (+ dX) form on the
  *                   warp-specialised kernel (DWS), 0 = the two-phase kernel
  *   "xw_ws_max"   : 1 (default) = the max adjoint with dX on DWS as well
@@ -475,7 +485,10 @@ size_t mgcn_spmm_xw_fwd_workspace_bytes(int32_t F_in, int32_t F_out);
  * (the adjoint of `x @ weight_node`, gcn_base_models.py:201, reassociated).
  * At F = 256 (fused_wide.hip) W is split once per call into a fragment
  * image in `workspace` (mgcn_spmm_xw_fwd_workspace_bytes; at 128 the
- * workspace may be NULL: it only holds the dynamic claim's counter), Y
+ * workspace may be NULL: it only holds the dynamic claim's counter, and
+ * without it the call runs the two-phase kernel, "xw_fwd_ws"; a hand-off of
+ * the warp-specialised kernel that gives up is reported as MGCN_EDEVICE by
+ * the next call), Y
  * needs 16-byte aligned rows, and relu_mask holds 8 words per row (feature f
  * at word 4 (f >> 7) + (f & 3), bit (f & 127) >> 2).
  */

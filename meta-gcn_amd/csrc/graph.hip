@@ -74,6 +74,7 @@ const char *device_error_what(unsigned code) {
     case kDevErrDws: return "spmm_xw_bwd_ws_kernel (128-wide adjoint)";
     case kDevErrWide: return "spmm_xw_wide_ws_kernel (256-wide layer)";
     case kDevErrPack: return "pack_rows_kernel (single-pass pack)";
+    case kDevErrFwdWs: return "spmm_xw_fwd_ws_kernel (128-wide forward)";
     default: return "unknown kernel";
   }
 }
