@@ -1034,6 +1034,79 @@ int mgcn_hatt_gather(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const in
                      const int32_t *col, const float *alpha, const float *Hp, int64_t ldh,
                      float *Y, int64_t ldy, void *stream);
 
+/* ------------------------------------------------ edge-gated node model */
+
+/*
+ * Edge-gated message passing: NodeModelAdditive with an EdgeGateProj /
+ * EdgeGateFree gate (src/gcn_meta/models/gcn_base_models.py:229-232, 322-396)
+ * after its x @ weight_node, and the adjoint.  Added under ABI 22 as the
+ * attention entries were (backward-compatible: the version stays 22).
+ *
+ * Hx = X W is [N, C] (row stride ldh).  For edge k (j -> i):
+ *   l_k = a[j] + c[i] + t_k,   g_k = sigmoid(l_k) = 1 / (1 + exp(-l_k)),
+ *   m_k = g_k w_k Hx[j],       Y[i] = reduce_{k -> i} m_k  (+ bias, ReLU).
+ * a = Hx w_src and c = Hx w_dst are per-node scores (mgcn_att_scores with
+ * H = 1 and a = [w_src | w_dst]); t is a per-slot term [nnz] in fwd slot
+ * order (edge features, free gates) or, with t_bcast != 0, one element read
+ * from the device and added to every slot (a scalar bias: no host sync);
+ * a, c and t are each NULL for an absent term (a and c together).  w are the
+ * per-slot message weights (NULL: ones); they do not enter the gate.
+ * Per-edge arrays (g, dl, dw, t, w, dg_in) are [nnz] in fwd slot order.
+ * Supported: 1 <= C <= 1024, nnz < 2^31, any leading dimension >= C; anything
+ * else returns MGCN_EINVAL before a launch.  n_rows == 0 is a successful
+ * no-op.  rowptr entries are absolute slot indices, so a row range [r0, r1) is
+ * the call with rowptr + r0, n_rows = r1 - r0 and the row-indexed arrays
+ * advanced by the caller (mgcn_gate_fwd: c, Y, argmax; mgcn_gate_bwd_dst: dY,
+ * dc; mgcn_gate_bwd_src: row_scale, dc, da, dHx); column- and slot-indexed
+ * arrays are passed as they are.  No atomics; slots keep
+ * COO order and every sum has a fixed order: results are bitwise repeatable.
+ */
+
+/*
+ * Forward over the fwd view (rows = destinations, col = sources):
+ * g written in slot order, Y[row] = epi(reduce_k g_k w_k Hx[col_k]) with
+ * reduce MGCN_REDUCE_SUM / MEAN (divided by max(degree, 1)) / MAX (`>=` in
+ * slot order: the later slot wins ties; an empty row gives 0), then + bias
+ * (NULL: none) and ReLU (relu != 0).  MAX writes argmax [n_rows, C]
+ * (contiguous): the winning edge's id eid[slot], -1 for an empty row -- the
+ * input of mgcn_max_mask; eid and argmax are not read otherwise.
+ */
+int mgcn_gate_fwd(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
+                  const int32_t *col, const int32_t *eid, const float *a, const float *c,
+                  const float *t, int t_bcast, const float *w, const float *Hx, int64_t ldh,
+                  int reduce, const float *bias, int relu, float *Y, int64_t ldy, float *g,
+                  int32_t *argmax, void *stream);
+
+/*
+ * Adjoint by destination row (fwd view), from dY [N, C] (ReLU / bias already
+ * taken back; mean: already divided by the row's count):
+ *   s_k  = sum_f dY[row,f] Hx[col_k,f]     (win_mask != NULL, max: over the
+ *          features whose winner bit of slot k is set)
+ *   dw_k = g_k s_k                          (dw NULL: not wanted)
+ *   dg_k = w_k s_k (+ dg_in[k]),   dl_k = dg_k g_k (1 - g_k)
+ *   dc[row] = sum_k dl_k                    (dc NULL: not wanted)
+ */
+int mgcn_gate_bwd_dst(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
+                      const int32_t *col, const float *Hx, int64_t ldh, const float *dY,
+                      int64_t lddy, const float *w, const float *g, const uint32_t *win_mask,
+                      const float *dg_in, float *dl, float *dc, float *dw, void *stream);
+
+/*
+ * Adjoint by source row (the bwd view rowptr_t / col_t, col_t = destinations;
+ * slot_map = mgcn_slot_map; g, dl and win_mask are in fwd slot order, w_t in
+ * bwd slot order):
+ *   da[row] = sum_k dl_k                                  (da NULL: not wanted)
+ *   dHx[row] = (sum_k g_k w_t_k dY[col_k]) [* row_scale[row]]
+ *              + da[row] w_sd[0:C] + dc[row] w_sd[C:2C]
+ * (max: dY restricted to the slot's winner bits; the rank-one terms only for
+ * da / dc given, w_sd = [w_src | w_dst] contiguous).
+ */
+int mgcn_gate_bwd_src(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr_t,
+                      const int32_t *col_t, const int32_t *slot_map, const float *dY,
+                      int64_t lddy, const float *w_t, const float *row_scale, const float *g,
+                      const float *dl, const uint32_t *win_mask, const float *w_sd,
+                      const float *dc, float *da, float *dHx, int64_t lddh, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

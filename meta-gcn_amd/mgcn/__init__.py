@@ -2,7 +2,8 @@
 jzhou316/meta-gcn) behind the reference's own module surface.
 
     mgcn.models : gcn_meta surface (NodeModelAdditive, NodeModelAttention,
-                  NodeModelHardAttention, GCNMultiKernel, GCNLayer, GCNModel, scatter_, activation)
+                  NodeModelHardAttention, NodeModelGatedAdditive, GCNMultiKernel,
+                  GCNLayer, GCNModel, scatter_, activation)
     mgcn.pyg    : PyG-1.x surface used by kernel/ (GCNConv, GINConv, SAGEConv,
                   GraphConv, global_mean_pool, JumpingKnowledge)
     mgcn.ops    : fused aggregation autograd ops
@@ -16,11 +17,11 @@ import torch  # noqa: F401  -- must be imported before libmgcn binds libamdhip64
 from . import _lib
 from ._lib import MgcnError, check_device, load, set_option
 from .graph import GraphPlan, build_plan, clear_cache, plan_for
-from .ops import (aggregate, attention_aggregate, hard_attention_aggregate, scatter_,
-                  segment_mean)
+from .ops import (aggregate, attention_aggregate, gate_aggregate, hard_attention_aggregate,
+                  scatter_, segment_mean)
 
 __version__ = "0.1.0"
 
 __all__ = ["MgcnError", "check_device", "load", "set_option", "GraphPlan", "build_plan", "plan_for",
-           "clear_cache", "aggregate", "attention_aggregate",
+           "clear_cache", "aggregate", "attention_aggregate", "gate_aggregate",
            "hard_attention_aggregate", "scatter_", "segment_mean", "_lib"]

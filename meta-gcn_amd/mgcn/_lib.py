@@ -151,6 +151,12 @@ SIGNATURES = {
                                  _vp, _vp, _int, _int, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mgcn_hatt_select": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
     "mgcn_hatt_gather": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "mgcn_gate_fwd": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _i64,
+                             _int, _vp, _int, _vp, _i64, _vp, _vp, _vp]),
+    "mgcn_gate_bwd_dst": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp]),
+    "mgcn_gate_bwd_src": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 class PackedTableC(ctypes.Structure):

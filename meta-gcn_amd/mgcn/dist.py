@@ -1152,6 +1152,9 @@ class ShardedGCNStack(torch.nn.Module):
                 len({(nm.deg_norm, nm.aggr) for nm in nms}) != 1:
             raise NotImplementedError("ShardedGCNStack: single-kernel layers with one deg_norm / "
                                       "aggr")
+        if any(getattr(nm, "edge_gate", None) is not None for nm in nms):
+            raise NotImplementedError("ShardedGCNStack: edge-gated layers are not sharded (the "
+                                      "gate reads rows of both endpoints)")
         acts = [layer.non_linear_name for layer in layers]
         if any(a not in ("relu", "none") for a in acts):
             raise NotImplementedError("ShardedGCNStack: 'relu' / 'none' layer activations")

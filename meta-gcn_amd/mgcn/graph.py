@@ -152,6 +152,15 @@ class GraphPlan:
     _slot_map: torch.Tensor | None = None
     _coo: tuple | None = None
     _last_slot: torch.Tensor | None = None
+    _fwd_eid64: torch.Tensor | None = None
+
+    def fwd_eid64(self) -> torch.Tensor:
+        """int64 [nnz]: ``fwd.eid`` as a torch index (COO edge id of every fwd
+        slot), converted on first use: the gate op permutes between COO and
+        slot order on every call."""
+        if self._fwd_eid64 is None:
+            self._fwd_eid64 = self.fwd.eid.long()
+        return self._fwd_eid64
 
     def last_edge_slot(self) -> torch.Tensor:
         """0-d int64 device tensor: the fwd-view slot of COO edge nnz - 1 (the

@@ -6,6 +6,8 @@ direction and the training scripts (src/run/train_botnet.py:190-294) run
 unchanged after swapping the import:
 
   NodeModelBase / NodeModelAdditive  gcn_base_models.py:11-243
+  EdgeGateProj / EdgeGateFree        gcn_base_models.py:322-396
+  NodeModelGatedAdditive             NodeModelAdditive with an edge gate
   NodeModelAttention                 graph_attention.py:11-123
   GCNMultiKernel                     gcn_multi_kernel.py:9-114
   GCNLayer / GCNModel                gcn_model.py:8-197
@@ -30,7 +32,7 @@ from torch.nn.utils.rnn import pad_sequence
 from . import _lib as L
 from .graph import plan_for
 from .ops import (aggregate_plan, attention_aggregate, gcn_layer, gcn_stack, linear, linear_bias,  # noqa: F401
-                  hard_attention_aggregate,
+                  gate_aggregate, hard_attention_aggregate,
                   residual_gcn_layer, residual_layer_supported, residual_stack,  # noqa: F401
                   scatter_)
 
@@ -105,12 +107,21 @@ class NodeModelBase(nn.Module):
         self.in_edgedim = in_edgedim
         self.deg_norm = deg_norm
         self.aggr = aggr
-        if edge_gate is not None:
-            # EdgeGateProj / EdgeGateFree (gcn_base_models.py:322-396) are
-            # outside the aggregation hot path this engine accelerates.
+        if edge_gate is not None and not self._gated:
+            # the plain class keeps its launch path; gates live in the subclass
             raise NotImplementedError(
-                "edge_gate is not supported by the mgcn engine (not on the Â·X hot path)")
-        self.register_parameter('edge_gate', None)
+                "edge_gate is not supported by NodeModelAdditive on the mgcn engine: use "
+                "NodeModelGatedAdditive (GCNMultiKernel / GCNLayer / GCNModel build it for "
+                "edge_gate='proj' / 'free')")
+        if edge_gate == 'proj':
+            self.edge_gate = EdgeGateProj(out_channels, in_edgedim=in_edgedim, bias=True)
+        elif edge_gate == 'free':
+            assert 'num_edges' in kwargs  # a fixed number of edges (gcn_base_models.py:60)
+            self.edge_gate = EdgeGateFree(kwargs['num_edges'])
+        else:
+            self.register_parameter('edge_gate', None)
+
+    _gated = False  # NodeModelGatedAdditive: True
 
     @staticmethod
     def degnorm_const(edge_index=None, num_nodes=None, deg=None, edge_weight=None, method='sm',
@@ -179,19 +190,165 @@ class NodeModelAdditive(NodeModelBase):
                       relu=False):
         """forward() with the caller's ReLU folded into the aggregation epilogue."""
         if edge_attr is not None:
-            raise NotImplementedError(
-                "edge_attr messages (gcn_base_models.py:204-227) are not supported by the "
-                "mgcn engine")
+            self._check_edge_attr(edge_attr, edge_index.size(1))
         plan = plan_for(edge_index, x.size(0))
         # deg_norm None ignores edge_weight entirely (gcn_base_models.py:209-211)
         norm = plan.norm(self.deg_norm, deg=deg,
                          edge_weight=edge_weight if self.deg_norm is not None else None)
+        if edge_attr is not None:
+            y = aggregate_plan(linear(x, self.weight_node), plan, norm, self.aggr)
+            return self._add_edge_messages(y, None, edge_attr, edge_index, relu)
         if self.aggr != 'max':
             # torch.matmul(x, W) (gcn_base_models.py:201) fused behind the
             # aggregation where the kernels apply
             return gcn_layer(x, self.weight_node, plan, norm, self.aggr, self.bias, relu)
         x = linear(x, self.weight_node)  # torch.matmul(x, W), gcn_base_models.py:201
         return aggregate_plan(x, plan, norm, self.aggr, self.bias, relu)
+
+    def _check_edge_attr(self, edge_attr, num_edges):
+        assert self.in_edgedim is not None  # gcn_base_models.py:205
+        if self.aggr == 'max':
+            raise NotImplementedError(
+                "aggr='max' with an edge_attr message term (gcn_base_models.py:204-227) is not "
+                "supported by the mgcn engine: max is not linear in the message, so the term "
+                "cannot be aggregated apart from the node rows")
+        if edge_attr.dim() != 2 or edge_attr.size(0) != num_edges:
+            raise ValueError(f"edge_attr must be [{num_edges}, {self.in_edgedim}], got "
+                             f"{tuple(edge_attr.shape)}")
+
+    def _add_edge_messages(self, y, g_coo, edge_attr, edge_index, relu):
+        """The edge-feature term of the messages (gcn_base_models.py:204-227)
+        by linearity of add / mean:  reduce_k g_k (edge_attr_k @ weight_edge) =
+        (reduce_k g_k edge_attr_k) @ weight_edge  (``g_coo`` None: ones), then
+        the bias, once, and the caller's ReLU."""
+        ea = edge_attr.to(torch.float32)
+        if g_coo is not None:
+            ea = g_coo.unsqueeze(1) * ea
+        ye = linear(scatter_(self.aggr, ea, edge_index[1], y.size(0)), self.weight_edge)
+        y = y + ye.to(y.dtype)
+        if self.bias is not None:
+            y = y + self.bias.to(y.dtype)
+        return torch.relu(y) if relu else y
+
+
+# ------------------------------------------------ gcn_base_models.py:322-396
+class EdgeGateProj(nn.Module):
+    """gcn_base_models.py:322-369: a sigmoid gate per edge from the projected
+    source row, target row and (optionally) edge features, plus a scalar bias.
+    Inside :class:`NodeModelGatedAdditive` the gate is formed in the gather
+    kernel; the standalone ``forward`` returns it as [E, 1] in COO order."""
+
+    def __init__(self, in_channels, in_edgedim=None, bias=False):
+        super().__init__()
+        self.in_channels = in_channels
+        self.in_edgedim = in_edgedim
+        self.linsrc = nn.Linear(in_channels, 1, bias=False)
+        self.lintgt = nn.Linear(in_channels, 1, bias=False)
+        if in_edgedim is not None:
+            self.linedge = nn.Linear(in_edgedim, 1, bias=False)
+        if bias:
+            self.bias = Parameter(torch.Tensor(1))  # a scalar bias applied to all edges
+        else:
+            self.register_parameter('bias', None)
+        self.reset_parameters()
+
+    def reset_parameters(self, initrange=0.1):
+        nn.init.uniform_(self.linsrc.weight, -initrange, initrange)
+        nn.init.uniform_(self.lintgt.weight, -initrange, initrange)
+        if self.in_edgedim is not None:
+            nn.init.uniform_(self.linedge.weight, -initrange, initrange)
+        if self.bias is not None:
+            nn.init.constant_(self.bias, 0)
+
+    def gate_terms(self, edge_attr, num_edges):
+        """(w_src, w_dst, t) of :func:`mgcn.ops.gate_aggregate`: t holds the
+        edge-feature projection and the bias (one element without edge
+        features, so the kernel reads it from the device)."""
+        t = self.bias
+        if edge_attr is not None:
+            assert self.in_edgedim is not None  # gcn_base_models.py:364
+            t = linear_bias(edge_attr.to(torch.float32), self.linedge.weight, None).view(-1)
+            if self.bias is not None:
+                t = t + self.bias
+        return self.linsrc.weight, self.lintgt.weight, t
+
+    def forward(self, x, edge_index, edge_attr=None, edge_weight=None):
+        # A rarely used path (the node model forms its gates in the gather
+        # kernel): it runs the whole gated aggregation, the Y gather over all
+        # C included, only to return g, and so inherits its C <= 1024 limit.
+        plan = plan_for(edge_index, x.size(0))
+        w_src, w_dst, t = self.gate_terms(edge_attr, plan.nnz)
+        g = gate_aggregate(x, plan, plan.norm(None), 'add', w_src, w_dst, t)[1]
+        return g.view(-1, 1)
+
+
+class EdgeGateFree(nn.Module):
+    """gcn_base_models.py:372-396: one free gate parameter per edge (a fixed
+    number of edges, in COO order)."""
+
+    def __init__(self, num_edges):
+        super().__init__()
+        self.num_edges = num_edges
+        self.edge_gates = Parameter(torch.Tensor(num_edges, 1))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.constant_(self.edge_gates, 1)
+
+    def check_edges(self, num_edges):
+        if num_edges != self.num_edges:
+            raise ValueError(f"EdgeGateFree holds {self.num_edges} gates, the graph has "
+                             f"{num_edges} edges")
+
+    def gate_terms(self, edge_attr, num_edges):
+        self.check_edges(num_edges)
+        return None, None, self.edge_gates.view(-1)
+
+    def forward(self, *args, **kwargs):
+        # standalone: no graph is given, so this is the parameter's own sigmoid
+        # (inside NodeModelGatedAdditive the gate kernel forms it per slot)
+        return torch.sigmoid(self.edge_gates)  # size (E, 1)
+
+
+class NodeModelGatedAdditive(NodeModelAdditive):
+    """gcn_base_models.py:163-243 with ``edge_gate`` 'proj' / 'free': every
+    message is multiplied by a learnt sigmoid gate of its edge.  Same
+    constructor, parameter names and forward signature as the reference's
+    NodeModelAdditive (``num_edges`` in ``**kwargs`` for 'free').  ``x @ W``
+    runs on :func:`mgcn.ops.linear`, the gate, the gather, the reduce, bias
+    and ReLU on :func:`mgcn.ops.gate_aggregate`; the gate needs the projected
+    rows themselves, so the layer is never reassociated to ``(A x) W``."""
+
+    _gated = True
+
+    def forward(self, x, edge_index, edge_attr=None, deg=None, edge_weight=None, gate_store=None,
+                **kwargs):
+        """``gate_store`` (a list) receives this call's gates, [E] in COO edge
+        order, detached."""
+        return self.forward_fused(x, edge_index, edge_attr, deg, edge_weight, relu=False,
+                                  gate_store=gate_store)
+
+    def forward_fused(self, x, edge_index, edge_attr=None, deg=None, edge_weight=None,
+                      relu=False, gate_store=None):
+        if self.edge_gate is None:
+            return super().forward_fused(x, edge_index, edge_attr, deg, edge_weight, relu)
+        if edge_attr is not None:
+            self._check_edge_attr(edge_attr, edge_index.size(1))
+        if isinstance(self.edge_gate, EdgeGateFree):
+            self.edge_gate.check_edges(edge_index.size(1))
+        plan = plan_for(edge_index, x.size(0))
+        norm = plan.norm(self.deg_norm, deg=deg,
+                         edge_weight=edge_weight if self.deg_norm is not None else None)
+        w_src, w_dst, t = self.edge_gate.gate_terms(edge_attr, plan.nnz)
+        hx = linear(x, self.weight_node)  # torch.matmul(x, W), gcn_base_models.py:201
+        if edge_attr is None:
+            y, g = gate_aggregate(hx, plan, norm, self.aggr, w_src, w_dst, t, self.bias, relu)
+        else:
+            y, g = gate_aggregate(hx, plan, norm, self.aggr, w_src, w_dst, t)
+            y = self._add_edge_messages(y, g, edge_attr, edge_index, relu)
+        if gate_store is not None:
+            gate_store.append(g.detach())
+        return y
 
 
 # ------------------------------------------------------ graph_attention.py
@@ -383,8 +540,11 @@ class GCNMultiKernel(nn.Module):
         if nodemodel not in self.nodemodel_dict:
             raise NotImplementedError(f"nodemodel={nodemodel!r} is not supported by mgcn")
         self.kernel_combine = kernel_combine
-        self.node_models = nn.ModuleList(
-            [self.nodemodel_dict[nodemodel](*args, **kwargs) for k in range(num_kernel)])
+        cls = self.nodemodel_dict[nodemodel]
+        edge_gate = kwargs.get('edge_gate', args[4] if len(args) > 4 else None)
+        if nodemodel == 'additive' and edge_gate is not None:
+            cls = NodeModelGatedAdditive
+        self.node_models = nn.ModuleList([cls(*args, **kwargs) for k in range(num_kernel)])
 
     def reset_parameters(self):
         for net in self.node_models:
@@ -422,8 +582,11 @@ class GCNMultiKernel(nn.Module):
         eis, eas, degs, ews = self._listify(edge_index_K, edge_attr_K, deg_K, edge_weight_K)
         if relu:
             assert self.can_fuse_relu(edge_index_K)
-            return self.node_models[0].forward_fused(x, eis[0], eas[0], degs[0], ews[0],
-                                                     relu=True)
+            nm = self.node_models[0]
+            if isinstance(nm, NodeModelGatedAdditive):
+                return nm.forward_fused(x, eis[0], eas[0], degs[0], ews[0], relu=True,
+                                        gate_store=kwargs.get('gate_store'))
+            return nm.forward_fused(x, eis[0], eas[0], degs[0], ews[0], relu=True)
         xo = None
         outs = []
         for nm, edge_index, edge_attr, deg, edge_weight in zip(self.node_models, eis, eas, degs,
@@ -432,6 +595,9 @@ class GCNMultiKernel(nn.Module):
                 continue
             if isinstance(nm, NodeModelAttention):
                 y = nm(x, edge_index, edge_attr, deg, edge_weight, **kwargs)  # attn_store
+            elif isinstance(nm, NodeModelGatedAdditive):
+                y = nm(x, edge_index, edge_attr, deg, edge_weight,
+                       gate_store=kwargs.get('gate_store'))
             else:
                 y = nm(x, edge_index, edge_attr, deg, edge_weight)
             outs.append(y)
@@ -474,7 +640,7 @@ class GCNLayer(nn.Module):
                 **kwargs):
         if self._relu and self.gcn.can_fuse_relu(edge_index_K):
             return self.gcn.forward_fused(x, edge_index_K, edge_attr_K, deg_K, edge_weight_K,
-                                          relu=True)
+                                          relu=True, **kwargs)  # gate_store
         xo = self.gcn(x, edge_index_K, edge_attr_K, deg_K, edge_weight_K, **kwargs)
         return self.non_linear(xo)
 
@@ -500,6 +666,8 @@ class GCNStack(nn.Module):
                 return None
             if not isinstance(g.node_models[0], NodeModelAdditive):
                 return None  # attention layers: layer by layer
+            if g.node_models[0].edge_gate is not None:
+                return None  # gated layers: layer by layer (the gate reads x W itself)
             nms.append(g.node_models[0])
         if len({(nm.deg_norm, nm.aggr) for nm in nms}) != 1:
             return None
@@ -607,6 +775,8 @@ class GCNModel(nn.Module):
                 return False
             if not isinstance(layer.gcn.node_models[0], NodeModelAdditive):
                 return False  # attention layers: step for step
+            if layer.gcn.node_models[0].edge_gate is not None:
+                return False  # gated layers: step for step
         return True
 
     def forward(self, x, edge_index_K, edge_attr_K=None, deg_K=None, edge_weight_K=None,
@@ -684,6 +854,7 @@ class GCNModel(nn.Module):
 
 
 __all__ = ["glorot", "zeros", "Identity", "activation", "scatter_", "Linear", "NodeModelBase",
-           "NodeModelAdditive", "NodeModelAttention", "NodeModelHardAttention",
+           "NodeModelAdditive", "EdgeGateProj", "EdgeGateFree", "NodeModelGatedAdditive",
+           "NodeModelAttention", "NodeModelHardAttention",
            "GCNMultiKernel", "GCNLayer", "GCNStack", "GCNModel"]
 _ = L  # keep the binding imported so a missing library fails at import of ops

@@ -37,6 +37,7 @@ from .ops_gemm import (SMALL_K, VENDOR_GEMMS, _Bmm, _bstr, _gemm_batched,  # noq
 from .ops_attention import (_AttentionAggregate, _HardAttentionEval,  # noqa: F401
                             _HardAttentionTrain, attention_aggregate,
                             hard_attention_aggregate)
+from .ops_gate import _GateAggregate, gate_aggregate  # noqa: F401
 from .ops_bf16 import (ROW_COPIES, _AggregateBf16, _SegmentReduceBf16,  # noqa: F401
                        relu_bwd_colsum_bf16, spmm_bf16_supported, spmm_bwd_bf16, spmm_fwd_bf16)
 from .ops_pack import (PACK_ROWS_WIDTHS, PackedTable, _SegmentMean, pack_rows,  # noqa: F401

@@ -1,0 +1,194 @@
+"""Edge-gated aggregation over a graph plan on libmgcn's gate kernels
+(csrc/edge_gate.hip).  Sits on :mod:`mgcn.ops_gemm` (the score vectors'
+gradients are one ``gemm_tn``, the ReLU / bias / mean adjoint is
+``relu_bwd_colsum``); :mod:`mgcn.ops` re-exports every name."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib as L
+from ._call import _contig_f32, launch
+from .graph import GraphPlan, NormPlan
+from .ops_gemm import gemm_tn, relu_bwd_colsum
+
+
+def _max_mask(plan: GraphPlan, argmax: torch.Tensor) -> torch.Tensor:
+    """Winner bits of every edge at its fwd slot (mgcn_max_mask), as
+    :func:`mgcn.ops.max_mask`."""
+    lib = L.load()
+    F = argmax.size(1)
+    dev = argmax.device
+    mask = torch.empty(max(plan.nnz, 1), (F + 31) // 32, dtype=torch.int32, device=dev)
+    launch(None, "mgcn_max_mask", dev, None, None, lib.mgcn_max_mask,
+           plan.fwd.n_rows, F, L.ptr(plan.fwd.rowptr), L.ptr(plan.fwd.eid), L.ptr(argmax),
+           L.ptr(mask), L.stream_of(dev))
+    return mask
+
+
+class _GateAggregate(torch.autograd.Function):
+    """The message passing of a gated NodeModelAdditive after its ``x @ W``
+    (gcn_base_models.py:209-241 with the gate of :322-396) on libmgcn's gate
+    kernels.
+
+    Forward: mgcn_att_scores (H = 1, the two gate vectors concatenated) when
+    the gate projects node rows, then one mgcn_gate_fwd launch (logit, sigmoid,
+    weighted gather, reduce, bias, ReLU); max: mgcn_max_mask on its argmax.
+    Saved: Hx, the gate (fwd slot order), the gate vectors, Y under ReLU, the
+    winner bits under max.  Backward: relu_bwd_colsum, mgcn_gate_bwd_dst,
+    mgcn_gate_bwd_src, and [da | dc]^T Hx as one mgcn_gemm_tn.
+
+    ``t`` is [E] in COO order or one element; ``w_fwd`` is ``norm.w_fwd`` as an
+    autograd input when the norm carries history (else None).  Returns
+    ``(Y, g_coo)``, both differentiable."""
+
+    @staticmethod
+    def forward(ctx, Hx, wsd, t, bias, w_fwd, plan: GraphPlan, norm: NormPlan, reduce: int,
+                relu: bool):
+        lib = L.load()
+        dev = Hx.device
+        N, C = Hx.shape
+        nnz = plan.nnz
+        st = L.stream_of(dev)
+        fwd = plan.fwd
+        eid = plan.fwd_eid64() if nnz else None
+        a = c = None
+        if wsd is not None:
+            wsd = wsd.detach().contiguous()
+            a = torch.empty(N, dtype=torch.float32, device=dev)
+            c = torch.empty(N, dtype=torch.float32, device=dev)
+            launch("att_scores", "mgcn_att_scores", dev, N, None, lib.mgcn_att_scores,
+                   N, 1, C, L.ptr(Hx), Hx.stride(0), L.ptr(wsd), L.ptr(a), L.ptr(c), st)
+        t_bcast = t is not None and t.numel() == 1
+        ts = None
+        if t is not None:
+            ts = t.detach().reshape(-1)
+            if not t_bcast:
+                ts = ts[eid] if nnz else ts
+            ts = ts.contiguous()
+        w = norm.w_fwd
+        w = None if w is None else w.detach().contiguous()
+        b = None if bias is None else bias.detach().to(torch.float32).contiguous()
+        Y = torch.empty(N, C, dtype=torch.float32, device=dev)
+        g = torch.empty(nnz, dtype=torch.float32, device=dev)
+        is_max = reduce == L.REDUCE_MAX
+        argmax = torch.empty(N, C, dtype=torch.int32, device=dev) if is_max else None
+        launch("gate_fwd", "mgcn_gate_fwd", dev, N, fwd.edges, lib.mgcn_gate_fwd,
+               N, nnz, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(fwd.eid), L.ptr(a), L.ptr(c),
+               L.ptr(ts), int(t_bcast), L.ptr(w), L.ptr(Hx), Hx.stride(0), reduce, L.ptr(b),
+               int(bool(relu)), L.ptr(Y), C, L.ptr(g), L.ptr(argmax), st)
+        mask = _max_mask(plan, argmax) if is_max else None
+        g_coo = torch.empty_like(g)
+        if nnz:
+            g_coo[eid] = g
+        ctx.plan, ctx.norm, ctx.reduce, ctx.relu = plan, norm, reduce, relu
+        ctx.t_shape, ctx.t_bcast = None if t is None else tuple(t.shape), t_bcast
+        ctx.has_bias = bias is not None
+        ctx.set_materialize_grads(False)  # an unused output sends None, not zeros
+        ctx.save_for_backward(Hx, wsd, g, Y if relu else None, mask)
+        return Y, g_coo
+
+    @staticmethod
+    def backward(ctx, dZ, dg_coo):
+        Hx, wsd, g, Y, mask = ctx.saved_tensors
+        plan, norm = ctx.plan, ctx.norm
+        lib = L.load()
+        dev = Hx.device
+        N, C = Hx.shape
+        nnz = plan.nnz
+        st = L.stream_of(dev)
+        fwd, bwd = plan.fwd, plan.bwd
+        eid = plan.fwd_eid64() if nnz else None
+        need_b = ctx.has_bias and ctx.needs_input_grad[3]
+        need_w = ctx.needs_input_grad[4]
+        mean = ctx.reduce == L.REDUCE_MEAN
+        if dZ is None:  # only the gates were used
+            dZ = torch.zeros(N, C, dtype=torch.float32, device=dev)
+        # mean: dY rows divided by their count once, as _Aggregate does
+        dY, db = relu_bwd_colsum(_contig_f32(dZ, "dY"), Y, ctx.relu, need_b,
+                                 row_div=plan.in_cnt if mean else None)
+        dg_in = None
+        if dg_coo is not None and nnz:
+            dg_in = dg_coo.to(torch.float32)[eid].contiguous()
+        proj = wsd is not None
+        w = norm.w_fwd
+        w = None if w is None else w.detach().contiguous()
+        dl = torch.empty(nnz, dtype=torch.float32, device=dev)
+        dc = torch.empty(N, dtype=torch.float32, device=dev) if proj else None
+        da = torch.empty(N, dtype=torch.float32, device=dev) if proj else None
+        dw = torch.empty(nnz, dtype=torch.float32, device=dev) if need_w else None
+        dHx = torch.empty(N, C, dtype=torch.float32, device=dev)
+        launch("gate_bwd_dst", "mgcn_gate_bwd_dst", dev, N, fwd.edges, lib.mgcn_gate_bwd_dst,
+               N, nnz, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hx), Hx.stride(0), L.ptr(dY),
+               dY.stride(0), L.ptr(w), L.ptr(g), L.ptr(mask), L.ptr(dg_in), L.ptr(dl), L.ptr(dc),
+               L.ptr(dw), st)
+        slot = plan.slot_map() if nnz else None
+        launch("gate_bwd_src", "mgcn_gate_bwd_src", dev, N, bwd.edges, lib.mgcn_gate_bwd_src,
+               N, nnz, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
+               dY.stride(0), L.ptr(norm.w_bwd), L.ptr(norm.row_scale_bwd), L.ptr(g), L.ptr(dl),
+               L.ptr(mask), L.ptr(wsd), L.ptr(dc), L.ptr(da), L.ptr(dHx), C, st)
+        dwsd = None
+        if proj and ctx.needs_input_grad[1]:
+            dwsd = gemm_tn(torch.stack([da, dc], dim=1), Hx).reshape(-1)  # [w_src | w_dst]
+        dt = None
+        if ctx.t_shape is not None and ctx.needs_input_grad[2]:
+            if ctx.t_bcast:
+                dt = dl.sum().reshape(ctx.t_shape)
+            else:
+                dt = torch.empty_like(dl)
+                if nnz:
+                    dt[eid] = dl
+                dt = dt.reshape(ctx.t_shape)
+        return dHx, dwsd, dt, db, dw, None, None, None, None
+
+
+def gate_aggregate(Hx: torch.Tensor, plan: GraphPlan, norm: NormPlan, aggr: str = "add",
+                   w_src: torch.Tensor | None = None, w_dst: torch.Tensor | None = None,
+                   t: torch.Tensor | None = None, bias: torch.Tensor | None = None,
+                   relu: bool = False):
+    """Gated aggregation (gcn_base_models.py:209-241 with the edge gates of
+    :322-396), fused: for edge k: j -> i
+
+        g_k = sigmoid(Hx[j] . w_src + Hx[i] . w_dst + t_k)
+        Y[i] = epi(reduce_{k -> i} g_k n_k Hx[j])
+
+    ``Hx`` [N, C] are the projected rows, ``w_src`` / ``w_dst`` ([C] or [1, C],
+    both or neither) the gate's two vectors, ``t`` a per-edge logit term [E] /
+    [E, 1] in COO order or one element added to every edge (None: none),
+    ``n_k`` the weights of ``norm`` (they do not enter the gate), ``aggr`` in
+    add / mean / max, bias and ReLU in the kernel's epilogue.
+
+    Returns ``(Y, g_coo)``: Y [N, C] and the gates [E] in COO order.  Both are
+    differentiable: in Hx, w_src, w_dst, t, bias and (a norm built with
+    ``grad``) the norm's weights; a gradient arriving on ``g_coo`` joins the
+    gate's own.  A bfloat16 ``Hx`` runs on the upcast rows and Y is rounded
+    once.  CPU tensors raise: no CPU path."""
+    L.require_device(Hx, plan.fwd.rowptr, w_src, w_dst, t, bias)
+    if aggr not in L.REDUCE_CODES:
+        raise ValueError(f"aggr must be one of add/mean/max, got {aggr!r}")
+    if Hx.dtype == torch.bfloat16:
+        Y, g = gate_aggregate(Hx.float(), plan, norm, aggr, w_src, w_dst, t, bias, relu)
+        return Y.to(torch.bfloat16), g
+    Hx = _contig_f32(Hx, "Hx")
+    N, C = Hx.shape
+    if N != plan.num_nodes:
+        raise ValueError(f"Hx has {N} rows, graph has {plan.num_nodes} nodes")
+    if not (1 <= C <= 1024 and plan.nnz < 2 ** 31):
+        raise L.MgcnError(f"gate_aggregate: unsupported shape (C = {C}, nnz = {plan.nnz}): "
+                          "need 1 <= C <= 1024, nnz < 2^31")
+    if (w_src is None) != (w_dst is None):
+        raise ValueError("gate_aggregate: w_src and w_dst come together")
+    wsd = None
+    if w_src is not None:
+        for name, v in (("w_src", w_src), ("w_dst", w_dst)):
+            if v.dtype != torch.float32 or v.numel() != C:
+                raise ValueError(f"{name} must be float32 with {C} entries, got {v.dtype} "
+                                 f"{tuple(v.shape)}")
+        wsd = torch.cat([w_src.reshape(-1), w_dst.reshape(-1)])
+    if t is not None:
+        if t.numel() not in (1, plan.nnz):
+            raise ValueError(f"t must have 1 or {plan.nnz} entries, got {tuple(t.shape)}")
+        t = t.to(torch.float32)
+    if bias is not None and bias.numel() != C:
+        raise ValueError(f"bias has {bias.numel()} entries, expected {C}")
+    return _GateAggregate.apply(Hx, wsd, t, bias, norm.w_fwd if norm.grad else None, plan, norm,
+                                L.REDUCE_CODES[aggr], bool(relu))
