@@ -1107,6 +1107,84 @@ int mgcn_gate_bwd_src(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *row
                       const float *dl, const uint32_t *win_mask, const float *w_sd,
                       const float *dc, float *da, float *dHx, int64_t lddh, void *stream);
 
+/* --------------------------------------------------- multi-kernel layers */
+
+/*
+ * GCNMultiKernel's additive layer (src/gcn_meta/models/gcn_multi_kernel.py:
+ * 76-114): K edge sets ("kernels") over one node set, each with its own
+ * weight_node, normalisation and bias, combined by add, mean (sum / K) or
+ * cat.  Added under ABI 22 as the attention and gate entries were
+ * (backward-compatible: the version stays 22).
+ *
+ * All K views are square over the same N nodes (n_rows == n_cols == N).
+ * H_all = x [W_0 | .. | W_{K-1}] is [N, K C] fp32 with row stride ldh; kernel
+ * k gathers its column block [k C, (k + 1) C).  The per-kernel arrays travel
+ * as one struct of pointer sets passed by value; entries k >= K are not read.
+ *
+ * Supported: 1 <= K <= MGCN_MULTI_MAX_K, reduce SUM / MEAN, any C >= 1 (the
+ * vector width, 4 / 2 / 1 floats, is the widest that C, both leading
+ * dimensions and both base addresses allow: block k starts k C floats into a
+ * row), any leading dimension that holds the row; n_rows == 0 is a successful
+ * no-op.  Anything else -- K outside the range, a view whose n_rows differs
+ * from the call's, reduce MAX, a short leading dimension, a NULL array --
+ * returns MGCN_EINVAL before a launch.  Rows are walked in natural order and
+ * there is no heavy-row path: the caller routes graphs with heavy rows to the
+ * per-kernel entries.  No atomics; slots keep COO order, kernels are combined
+ * in index order, every product, sum and division is rounded on its own:
+ * results are bitwise repeatable and equal the K single-kernel calls below.
+ */
+#define MGCN_MULTI_MAX_K 8
+#define MGCN_COMBINE_ADD 0
+#define MGCN_COMBINE_MEAN 1
+#define MGCN_COMBINE_CAT 2
+
+typedef struct mgcn_multi_views {
+  int64_t n_rows[MGCN_MULTI_MAX_K];          /* rows of view k: must equal the call's n_rows */
+  const int64_t *rowptr[MGCN_MULTI_MAX_K];   /* [n_rows + 1] */
+  const int32_t *col[MGCN_MULTI_MAX_K];      /* [nnz_k] (may be NULL when nnz_k == 0) */
+  const float *w[MGCN_MULTI_MAX_K];          /* [nnz_k] per-slot weights, NULL: ones */
+  const float *bias[MGCN_MULTI_MAX_K];       /* forward: [C], NULL: none */
+  const float *cnt[MGCN_MULTI_MAX_K];        /* adjoint, MEAN: max(in-degree_k, 1) [N] */
+  const float *row_scale[MGCN_MULTI_MAX_K];  /* adjoint: [n_rows] post-scale, NULL: none */
+} mgcn_multi_views;
+
+/*
+ * Forward over the K fwd views (rows = destinations).  For row i, feature f:
+ *   for k = 0 .. K-1, in kernel order:
+ *     s = 0; for the slots of view k's row i, in slot order:
+ *       s = s + H_all[col, k C + f] * w_k[slot]
+ *     reduce MEAN:  s = s / max(deg_k(i), 1)
+ *     bias_k != NULL:  s = s + bias_k[f]
+ *     combine ADD / MEAN:  y = (k == 0) ? s : y + s
+ *     combine CAT:         Y[i, k C + f] = relu ? max(s, 0) : s
+ *   combine MEAN:  y = y / (float)K
+ *   ADD / MEAN:  Y[i, f] = relu ? max(y, 0) : y
+ * i.e. mgcn_spmm_fwd per kernel on the column-block views, then the
+ * reference's left-to-right `xo +=`, bit for bit.  A row that is empty in view
+ * k contributes 0 + bias_k.  Y is [n_rows, C] (CAT: [n_rows, K C]), row
+ * stride ldy.
+ */
+int mgcn_multi_spmm_fwd(int64_t n_rows, int32_t K, int32_t C, mgcn_multi_views views,
+                        const float *H_all, int64_t ldh, float *Y, int64_t ldy, int reduce,
+                        int combine, int relu, void *stream);
+
+/*
+ * Adjoint over the K bwd views (rows = sources, col = destinations, w in bwd
+ * slot order).  For source row s, kernel k, feature f:
+ *   acc = 0; for the slots of view k's row s, in slot order:
+ *     g = dY[col, (CAT ? k C : 0) + f]
+ *     combine MEAN:  g = g / (float)K
+ *     reduce MEAN:   g = g / cnt_k[col]
+ *     acc = acc + g * w_k[slot]
+ *   dH_all[s, k C + f] = acc [* row_scale_k[s]]
+ * i.e. K mgcn_spmm_bwd calls (SUM, or MEAN with cnt) on dY / comb_div (true
+ * divisions) into the column blocks of dH_all [n_rows, K C], row stride lddh.
+ * dY has the ReLU and bias already taken back.
+ */
+int mgcn_multi_spmm_bwd(int64_t n_rows, int32_t K, int32_t C, mgcn_multi_views views_t,
+                        const float *dY, int64_t lddy, float *dH_all, int64_t lddh, int reduce,
+                        int combine, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

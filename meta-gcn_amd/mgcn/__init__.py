@@ -18,10 +18,10 @@ from . import _lib
 from ._lib import MgcnError, check_device, load, set_option
 from .graph import GraphPlan, build_plan, clear_cache, plan_for
 from .ops import (aggregate, attention_aggregate, gate_aggregate, hard_attention_aggregate,
-                  scatter_, segment_mean)
+                  multi_aggregate, scatter_, segment_mean)
 
 __version__ = "0.1.0"
 
 __all__ = ["MgcnError", "check_device", "load", "set_option", "GraphPlan", "build_plan", "plan_for",
            "clear_cache", "aggregate", "attention_aggregate", "gate_aggregate",
-           "hard_attention_aggregate", "scatter_", "segment_mean", "_lib"]
+           "multi_aggregate", "hard_attention_aggregate", "scatter_", "segment_mean", "_lib"]

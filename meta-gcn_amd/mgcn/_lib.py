@@ -33,6 +33,19 @@ _int = ctypes.c_int
 _sz = ctypes.c_size_t
 _f32 = ctypes.c_float
 
+MULTI_MAX_K = 8
+COMBINE_CODES = {"add": 0, "mean": 1, "cat": 2}
+
+
+class MultiViewsC(ctypes.Structure):
+    """include/mgcn.h mgcn_multi_views (passed by value)."""
+    _fields_ = [("n_rows", ctypes.c_int64 * MULTI_MAX_K),
+                ("rowptr", ctypes.c_void_p * MULTI_MAX_K), ("col", ctypes.c_void_p * MULTI_MAX_K),
+                ("w", ctypes.c_void_p * MULTI_MAX_K), ("bias", ctypes.c_void_p * MULTI_MAX_K),
+                ("cnt", ctypes.c_void_p * MULTI_MAX_K),
+                ("row_scale", ctypes.c_void_p * MULTI_MAX_K)]
+
+
 # name -> (restype, argtypes); every symbol include/mgcn.h declares
 SIGNATURES = {
     "mgcn_abi_version": (_int, []),
@@ -157,6 +170,10 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _vp, _vp]),
     "mgcn_gate_bwd_src": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mgcn_multi_spmm_fwd": (_int, [_i64, _i32, _i32, MultiViewsC, _vp, _i64, _vp, _i64, _int, _int,
+                                   _int, _vp]),
+    "mgcn_multi_spmm_bwd": (_int, [_i64, _i32, _i32, MultiViewsC, _vp, _i64, _vp, _i64, _int, _int,
+                                   _vp]),
 }
 
 class PackedTableC(ctypes.Structure):

@@ -30,9 +30,11 @@ from torch.nn import Parameter
 from torch.nn.utils.rnn import pad_sequence
 
 from . import _lib as L
+from . import ops as _ops
 from .graph import plan_for
 from .ops import (aggregate_plan, attention_aggregate, gcn_layer, gcn_stack, linear, linear_bias,  # noqa: F401
-                  gate_aggregate, hard_attention_aggregate,
+                  gate_aggregate, hard_attention_aggregate, multi_aggregate, multi_kernel_fusable,
+                  multi_kernel_reason,
                   residual_gcn_layer, residual_layer_supported, residual_stack,  # noqa: F401
                   scatter_)
 
@@ -528,7 +530,14 @@ class NodeModelHardAttention(NodeModelBase):
 class GCNMultiKernel(nn.Module):
     """gcn_multi_kernel.py:9-114.  The 'additive' and 'attention' node models
     run on this engine; 'hardattention' is not registered here yet
-    (:class:`NodeModelHardAttention` exists and is used directly)."""
+    (:class:`NodeModelHardAttention` exists and is used directly).
+
+    Two to eight plain additive kernels (add / mean, no gate, no edge_attr,
+    fp32 rows, no heavy rows, no gradient asked of deg / edge_weight) run as
+    one GEMM and one launch per direction (:meth:`_forward_multi`,
+    :func:`mgcn.ops.multi_kernel_fusable`); everything else is the loop over
+    the node models.  'mean' divides by the number of kernels with edges and
+    'cat' concatenates (the reference raises for both when K > 1)."""
 
     nodemodel_dict = {'additive': NodeModelAdditive, 'attention': NodeModelAttention}
 
@@ -571,22 +580,71 @@ class GCNMultiKernel(nn.Module):
                                   **kwargs)
 
     def can_fuse_relu(self, edge_index_K) -> bool:
+        """The layer's ReLU can ride in forward_fused: a single additive kernel
+        (its aggregation's epilogue), or a module the fused multi-kernel route
+        may take (there the ReLU follows the combine in the launch; a call the
+        route declines applies it after the loop)."""
         if isinstance(edge_index_K, torch.Tensor):
             edge_index_K = [edge_index_K]
-        return len(self.node_models) == 1 and len(edge_index_K) == 1 \
-            and edge_index_K[0] is not None \
-            and all(isinstance(nm, NodeModelAdditive) for nm in self.node_models)
+        if len(self.node_models) == 1 and len(edge_index_K) == 1:
+            return edge_index_K[0] is not None \
+                and all(isinstance(nm, NodeModelAdditive) for nm in self.node_models)
+        nms = [nm for nm, ei in zip(self.node_models, edge_index_K) if ei is not None]
+        return _ops._FUSE_MULTI and 2 <= len(nms) <= L.MULTI_MAX_K \
+            and all(type(nm) is NodeModelAdditive and nm.aggr in ('add', 'mean') for nm in nms)
+
+    def _multi_reason(self, x, eis, eas):
+        """:func:`mgcn.ops.multi_kernel_reason` of this module on this call
+        (what is known before a plan is built)."""
+        nms = [nm for nm, ei in zip(self.node_models, eis) if ei is not None]
+        return multi_kernel_reason(
+            x, len(nms), nms[0].aggr if nms else 'add',
+            plain=all(type(nm) is NodeModelAdditive for nm in nms),
+            edge_attr=any(ea is not None for ei, ea in zip(eis, eas) if ei is not None))
+
+    def _forward_multi(self, x, eis, eas, degs, ews, relu):
+        """The K kernels in one launch per direction (gcn_multi_kernel.py:93-112
+        on :func:`mgcn.ops.multi_aggregate`): one GEMM x @ [W_0 | .. | W_{K-1}]
+        reads x once, the kernels' results are combined (and the ReLU applied)
+        in registers, and the backward is one adjoint launch and one dense
+        backward.  None when the route does not apply
+        (:func:`mgcn.ops.multi_kernel_fusable`): the caller runs the loop."""
+        if not _ops._FUSE_MULTI or self._multi_reason(x, eis, eas) is not None \
+                or _wants_norm_grad(degs, ews):
+            return None
+        present = [t for t in zip(self.node_models, eis, degs, ews) if t[1] is not None]
+        nms = [t[0] for t in present]
+        plans = [plan_for(ei, x.size(0)) for _, ei, _, _ in present]
+        # deg_norm None ignores edge_weight entirely (gcn_base_models.py:209-211)
+        norms = [plan.norm(nm.deg_norm, deg=deg, edge_weight=ew if nm.deg_norm is not None else None)
+                 for plan, (nm, _, deg, ew) in zip(plans, present)]
+        if not multi_kernel_fusable(x, plans, norms, nms[0].aggr,
+                                    out_channels=nms[0].out_channels):
+            return None
+        h_all = linear(x, torch.cat([nm.weight_node for nm in nms], dim=1))
+        return multi_aggregate(h_all, plans, norms, [nm.bias for nm in nms], nms[0].aggr,
+                               self.kernel_combine, relu)
 
     def forward_fused(self, x, edge_index_K, edge_attr_K=None, deg_K=None, edge_weight_K=None,
                       relu=False, **kwargs):
         eis, eas, degs, ews = self._listify(edge_index_K, edge_attr_K, deg_K, edge_weight_K)
         if relu:
             assert self.can_fuse_relu(edge_index_K)
+        if relu and len(self.node_models) == 1:
             nm = self.node_models[0]
             if isinstance(nm, NodeModelGatedAdditive):
                 return nm.forward_fused(x, eis[0], eas[0], degs[0], ews[0], relu=True,
                                         gate_store=kwargs.get('gate_store'))
             return nm.forward_fused(x, eis[0], eas[0], degs[0], ews[0], relu=True)
+        if len(self.node_models) > 1:
+            y = self._forward_multi(x, eis, eas, degs, ews, relu)
+            if y is not None:
+                return y
+        xo = self._forward_loop(x, eis, eas, degs, ews, **kwargs)
+        return torch.relu(xo) if relu else xo
+
+    def _forward_loop(self, x, eis, eas, degs, ews, **kwargs):
+        """One node model call per kernel, combined as gcn_multi_kernel.py:93-112."""
         xo = None
         outs = []
         for nm, edge_index, edge_attr, deg, edge_weight in zip(self.node_models, eis, eas, degs,
@@ -618,7 +676,9 @@ class GCNMultiKernel(nn.Module):
 # -------------------------------------------------------------- gcn_model.py
 class GCNLayer(nn.Module):
     """gcn_model.py:128-197; a ReLU layer activation is fused into the
-    aggregation epilogue when there is a single kernel."""
+    aggregation epilogue when there is a single kernel, and into the fused
+    multi-kernel launch (after the combine) when there are several plain
+    additive ones (:meth:`GCNMultiKernel.can_fuse_relu`)."""
 
     def __init__(self, in_channels, out_channels, in_edgedim=None, deg_norm='sm', edge_gate=None,
                  aggr='add', bias=True, num_kernel=1, nodemodel='additive', non_linear='relu',

@@ -38,6 +38,8 @@ from .ops_attention import (_AttentionAggregate, _HardAttentionEval,  # noqa: F4
                             _HardAttentionTrain, attention_aggregate,
                             hard_attention_aggregate)
 from .ops_gate import _GateAggregate, gate_aggregate  # noqa: F401
+from .ops_multi import (_MultiAggregate, multi_aggregate, multi_kernel_fusable,  # noqa: F401
+                        multi_kernel_reason, multi_spmm_bwd, multi_spmm_fwd)
 from .ops_bf16 import (ROW_COPIES, _AggregateBf16, _SegmentReduceBf16,  # noqa: F401
                        relu_bwd_colsum_bf16, spmm_bf16_supported, spmm_bwd_bf16, spmm_fwd_bf16)
 from .ops_pack import (PACK_ROWS_WIDTHS, PackedTable, _SegmentMean, pack_rows,  # noqa: F401
@@ -55,6 +57,11 @@ def __getattr__(name):
 # (mgcn_spmm_xw_fwd); MGCN_FUSE_XW=0 selects the GEMM + SpMM launches
 _FUSE_XW = os.environ.get("MGCN_FUSE_XW", "1") != "0"
 
+# one launch per direction for a multi-kernel layer (mgcn_multi_spmm_fwd /
+# _bwd, :func:`multi_kernel_fusable`); MGCN_FUSE_MULTI=0 keeps the loop over
+# the kernels
+_FUSE_MULTI = os.environ.get("MGCN_FUSE_MULTI", "1") != "0"
+
 
 # The route switches of a GCN stack: :func:`_plan_stack` reads them, once per
 # forward, and says what each one selects.
@@ -70,6 +77,13 @@ def set_fused_layers(enabled: bool) -> None:
     kernels (mgcn_spmm_xw_fwd / _bwd) where they apply."""
     global _FUSE_XW
     _FUSE_XW = bool(enabled)
+
+
+def set_fused_multi_kernel(enabled: bool) -> None:
+    """Use (True, the default) or bypass the fused multi-kernel route of
+    :class:`mgcn.models.GCNMultiKernel` (:func:`multi_kernel_fusable`)."""
+    global _FUSE_MULTI
+    _FUSE_MULTI = bool(enabled)
 
 
 def set_z_middle(enabled: bool) -> None:
