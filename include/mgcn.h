@@ -1185,6 +1185,51 @@ int mgcn_multi_spmm_bwd(int64_t n_rows, int32_t K, int32_t C, mgcn_multi_views v
                         const float *dY, int64_t lddy, float *dH_all, int64_t lddh, int reduce,
                         int combine, void *stream);
 
+/*
+ * Derived plans: a CSR view of an edge subset of a graph that already has one
+ * (derive.hip), without a sort, an index check or a host wait.  The child keeps
+ * the parent's row grouping and the COO order inside each row, so its view is
+ * a stable stream compaction of the parent's: flags, an exclusive prefix sum,
+ * a scatter.  The result is what mgcn_csr_build gives for the filtered (and
+ * relabelled) edge list.
+ *
+ * mgcn_edge_rank: eid_new[e] = rank of COO edge e among the surviving edges,
+ * -1 where it is dropped; *total (a device word) = their number.  An edge
+ * survives iff keep[e] != 0 (keep NULL: every edge) and, where node maps are
+ * given, both endpoints map to >= 0.  An endpoint's map comes with the slots
+ * (col, eid) of the view whose COLUMNS are that endpoint: map_a[col_a[k]] is
+ * tested for edge eid_a[k] (the fwd view holds the sources, the bwd view the
+ * destinations).  Either map may be NULL (no filter on that endpoint, its
+ * view is not read).
+ */
+size_t mgcn_edge_rank_workspace_bytes(int64_t nnz);
+int mgcn_edge_rank(int64_t nnz, const uint8_t *keep, const int32_t *col_a, const int32_t *eid_a,
+                   const int32_t *map_a, const int32_t *col_b, const int32_t *eid_b,
+                   const int32_t *map_b, int32_t *eid_new, int64_t *total, void *workspace,
+                   size_t workspace_bytes, void *stream);
+
+/*
+ * mgcn_csr_derive: parent slot k of parent row p is kept iff
+ * eid_new[eid[k]] >= 0.  Output rows r = 0 .. n_rows_out - 1 are the parent
+ * rows row_src[r] (every kept slot must lie in one of them, each parent row
+ * at most once); inside a row the kept slots keep the parent's order.
+ * col_out = col_map[col[k]], eid_out = eid_new[eid[k]],
+ * rowptr_out[n_rows_out] = nnz_out.  The parent's arrays are trusted (they
+ * come from mgcn_csr_build); stores past nnz_out entries are suppressed.
+ * nnz_in == 0 or nnz_out == 0: rowptr_out is zeroed, nothing else runs.
+ */
+size_t mgcn_csr_derive_workspace_bytes(int64_t n_rows_in, int64_t n_rows_out, int64_t nnz_in);
+int mgcn_csr_derive(
+    int64_t n_rows_in, int64_t n_cols_in, int64_t nnz_in,
+    const int64_t *rowptr, const int32_t *col, const int32_t *eid, /* one view of the parent */
+    const int32_t *row_src, /* [n_rows_out] parent row of each output row; NULL: identity */
+    int64_t n_rows_out,
+    const int32_t *col_map, /* [n_cols_in] new id of a parent column, -1: dropped; NULL: identity */
+    const int32_t *eid_new, /* [nnz_in] new COO id of each parent COO edge, -1: dropped */
+    int64_t nnz_out,        /* number of eid_new entries >= 0 */
+    int64_t *rowptr_out, int32_t *col_out, int32_t *eid_out,
+    void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,8 @@ import torch  # noqa: F401  -- must be imported before libmgcn binds libamdhip64
 
 from . import _lib
 from ._lib import MgcnError, check_device, load, set_option
-from .graph import GraphPlan, build_plan, clear_cache, plan_for
+from .graph import (GraphPlan, adopt_plan, build_plan, clear_cache, drop_edges, plan_for,
+                    set_derived_plans)
 from .ops import (aggregate, attention_aggregate, gate_aggregate, hard_attention_aggregate,
                   multi_aggregate, scatter_, segment_mean)
 
@@ -24,4 +25,5 @@ __version__ = "0.1.0"
 
 __all__ = ["MgcnError", "check_device", "load", "set_option", "GraphPlan", "build_plan", "plan_for",
            "clear_cache", "aggregate", "attention_aggregate", "gate_aggregate",
-           "multi_aggregate", "hard_attention_aggregate", "scatter_", "segment_mean", "_lib"]
+           "multi_aggregate", "hard_attention_aggregate", "scatter_", "segment_mean", "_lib",
+           "adopt_plan", "drop_edges", "set_derived_plans"]

@@ -174,6 +174,11 @@ SIGNATURES = {
                                    _int, _vp]),
     "mgcn_multi_spmm_bwd": (_int, [_i64, _i32, _i32, MultiViewsC, _vp, _i64, _vp, _i64, _int, _int,
                                    _vp]),
+    "mgcn_edge_rank_workspace_bytes": (_sz, [_i64]),
+    "mgcn_edge_rank": (_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mgcn_csr_derive_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "mgcn_csr_derive": (_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp,
+                               _vp, _vp, _vp, _sz, _vp]),
 }
 
 class PackedTableC(ctypes.Structure):

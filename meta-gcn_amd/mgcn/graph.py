@@ -24,6 +24,8 @@ so this engine prepares them once.
 """
 from __future__ import annotations
 
+import dataclasses
+import os
 import weakref
 from collections import OrderedDict
 from dataclasses import dataclass, field
@@ -231,6 +233,90 @@ class GraphPlan:
         if len(self.norms) > 8:
             self.norms.pop(next(iter(self.norms)))
         return plan
+
+    # ---------------------------------------------------------- derived plans
+    def edge_index(self) -> torch.Tensor:
+        """int64 [2, nnz]: the COO edge list, in edge id order (from :meth:`coo`)."""
+        return torch.stack(self.coo(), dim=0)
+
+    def reversed(self) -> "GraphPlan":
+        """The plan of ``edge_index.flip(0)``: the two views swapped (they share
+        their arrays with this plan), ``in_cnt`` of the new destinations.  No
+        kernel runs."""
+        fwd, bwd = dataclasses.replace(self.bwd), dataclasses.replace(self.fwd)
+        in_cnt = (fwd.rowptr[1:] - fwd.rowptr[:-1]).clamp_(min=1).to(torch.float32)
+        return GraphPlan(num_nodes=self.num_nodes, nnz=self.nnz, device=self.device, fwd=fwd,
+                         bwd=bwd, in_cnt=in_cnt)
+
+    def select_edges(self, keep: torch.Tensor) -> "GraphPlan":
+        """The plan of ``edge_index[:, keep]`` on the same nodes: ``keep`` is a
+        bool [nnz] on the device, in COO edge order; a kept edge's new id is
+        its rank among the kept.  Equals ``build_plan`` of that edge list field
+        for field, without its sorts (libmgcn ``mgcn_csr_derive``).  One host
+        wait, for the number of kept edges."""
+        keep = _keep_mask(keep, self.nnz)
+        _same_device(self, keep)
+        eid_new, total = _edge_rank(self, keep, None)
+        return _derive(self, eid_new, int(total), self.num_nodes, None, None)
+
+    def induced(self, nodes, relabel: bool = False, validate: bool = True) -> "GraphPlan":
+        """The plan of the subgraph induced by ``nodes``, a bool mask
+        [num_nodes] or a list of node ids in any order.
+
+        ``relabel=False`` keeps the node count and ids (the edges with both
+        endpoints in the set: ``votepool.subgraph(..., relabel_nodes=False)``);
+        ``relabel=True`` has ``len(nodes)`` nodes, the new id of a node being
+        its position in the list (a mask: ascending) -- ``pool.filter_adj`` and
+        ``subgraph(..., relabel_nodes=True)``.  Ids out of range or repeated
+        raise ValueError before a view is derived (``validate=False``: the
+        caller vouches for them, e.g. the output of ``unique`` or ``topk``)."""
+        n = self.num_nodes
+        if not isinstance(nodes, torch.Tensor):
+            nodes = torch.as_tensor(nodes, device=self.device)
+        checks = None
+        if nodes.dtype in (torch.bool, torch.uint8):
+            if nodes.dim() != 1 or nodes.numel() != n:
+                raise ValueError(f"induced: node mask has shape {tuple(nodes.shape)}, "
+                                 f"expected ({n},)")
+            _same_device(self, nodes)
+            mask = nodes.to(torch.bool)
+            if relabel:
+                row_src = mask.nonzero().view(-1).to(torch.int32)
+                n_out = int(row_src.numel())
+                node_map = (mask.cumsum(0, dtype=torch.int32) - 1).masked_fill_(~mask, -1)
+        else:
+            if nodes.dtype not in (torch.int64, torch.int32) or nodes.dim() != 1:
+                raise ValueError("induced: nodes must be a bool mask or a 1-d list of integer ids")
+            ids = nodes.to(torch.int64)
+            if validate:
+                safe = ids.clamp(0, max(n - 1, 0))
+                cnt = torch.zeros(max(n, 1), dtype=torch.int32, device=ids.device)
+                cnt.index_add_(0, safe, torch.ones_like(safe, dtype=torch.int32))
+                checks = torch.stack([((ids < 0) | (ids >= n)).any(), (cnt > 1).any()])
+                if ids.device.type != "cuda":
+                    _raise_bad_ids(checks.tolist(), n)
+                ids = safe
+            _same_device(self, ids)
+            if relabel:
+                row_src = ids.to(torch.int32)
+                n_out = int(ids.numel())
+                node_map = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+                node_map[ids] = torch.arange(n_out, dtype=torch.int32, device=self.device)
+            else:
+                mask = torch.zeros(n, dtype=torch.bool, device=self.device)
+                mask[ids] = True
+        if not relabel:
+            row_src, n_out = None, n
+            node_map = mask.to(torch.int32) - 1  # 0 in the set, -1 outside: a filter only
+        eid_new, total = _edge_rank(self, None, node_map)
+        if checks is not None:
+            # the id checks ride in the one read of the edge count
+            got = torch.cat([total.view(1), checks.to(torch.int64)]).tolist()
+            _raise_bad_ids(got[1:], n)
+            nnz_out = int(got[0])
+        else:
+            nnz_out = int(total)
+        return _derive(self, eid_new, nnz_out, n_out, node_map if relabel else None, row_src)
 
 
 def _tkey(t: torch.Tensor | None):
@@ -454,3 +540,174 @@ def plan_for(edge_index: torch.Tensor, num_nodes: int) -> GraphPlan:
 
 def clear_cache() -> None:
     _CACHE.clear()
+
+
+def cached_plan(edge_index: torch.Tensor, num_nodes: int) -> GraphPlan | None:
+    """The plan :func:`plan_for` would return without building one, or None."""
+    hit = _CACHE.get(cache_key(edge_index, num_nodes))
+    return hit[1] if hit is not None and hit[0]() is edge_index else None
+
+
+def adopt_plan(edge_index: torch.Tensor, num_nodes: int, plan: GraphPlan) -> GraphPlan:
+    """Register ``plan`` (a derived plan of exactly this edge list) as the
+    :func:`plan_for` result of ``edge_index``, under the same key and
+    weak-reference rules: the entry is valid while this very tensor is alive
+    and unmodified.  For modules that hand ``edge_index`` tensors on."""
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError(f"edge_index must be [2, E], got {tuple(edge_index.shape)}")
+    if int(plan.num_nodes) != int(num_nodes) or int(plan.nnz) != int(edge_index.size(1)):
+        raise ValueError(f"adopt_plan: the plan has {plan.num_nodes} nodes / {plan.nnz} edges, "
+                         f"edge_index {int(num_nodes)} / {int(edge_index.size(1))}")
+    key = cache_key(edge_index, num_nodes)
+    _CACHE[key] = (weakref.ref(edge_index), plan)
+    _CACHE.move_to_end(key)
+    while len(_CACHE) > _CACHE_SIZE:
+        _CACHE.popitem(last=False)
+    return plan
+
+
+# ----------------------------------------------------------- derived plans
+# Pooling modules derive the plan of the subgraph they return from the plan of
+# their input graph (adopt_derived) and adopt it for the edge_index they
+# hand on, so the next layer's plan_for is a cache hit instead of two sorts;
+# MGCN_DERIVED_PLANS=0 keeps the rebuild everywhere.
+_DERIVED_PLANS = os.environ.get("MGCN_DERIVED_PLANS", "1") != "0"
+
+
+def set_derived_plans(enabled: bool) -> None:
+    """Derive (True, the default) or rebuild (False) the plans of the
+    subgraphs that ``votepool.prune`` and TopK / SAG pooling return."""
+    global _DERIVED_PLANS
+    _DERIVED_PLANS = bool(enabled)
+
+
+def derived_plans_enabled() -> bool:
+    return _DERIVED_PLANS
+
+
+def adopt_derived(parent_edge_index: torch.Tensor, parent_nodes: int, keep: torch.Tensor,
+                  child_edge_index: torch.Tensor, child_nodes: int,
+                  nodes: torch.Tensor | None = None, node_map: torch.Tensor | None = None) -> None:
+    """The pooling modules' hook.  ``child_edge_index`` is what their torch
+    code made of ``parent_edge_index``: the edges ``keep`` (bool [E], any node
+    filter already in it), in order, and -- with ``nodes`` -- relabelled to
+    positions in that list of valid, distinct ids (``node_map``: the new id of
+    every parent node, -1 outside, when the caller has it).  If the parent has
+    a cached plan (and derived plans are on), the child's plan is derived from
+    it and adopted for ``child_edge_index``; the edge count is the tensor's,
+    so no host wait is added."""
+    if not _DERIVED_PLANS or child_edge_index.device.type != "cuda":
+        return
+    parent = cached_plan(parent_edge_index, parent_nodes)
+    if parent is None:
+        return
+    eid_new, _ = _edge_rank(parent, _keep_mask(keep, parent.nnz), None)
+    row_src = None
+    if nodes is not None:
+        row_src = nodes.to(torch.int32)
+        if node_map is None:
+            node_map = torch.full((parent.num_nodes,), -1, dtype=torch.int32, device=parent.device)
+            node_map[nodes] = torch.arange(int(nodes.numel()), dtype=torch.int32,
+                                           device=parent.device)
+        node_map = node_map.to(torch.int32)
+    child = _derive(parent, eid_new, int(child_edge_index.size(1)), int(child_nodes), node_map,
+                    row_src)
+    adopt_plan(child_edge_index, child_nodes, child)
+
+
+def drop_edges(plan: GraphPlan, p: float, generator: torch.Generator | None = None):
+    """DropEdge: every edge is dropped independently with probability ``p``
+    (a Bernoulli keep mask drawn on the device, then
+    :meth:`GraphPlan.select_edges`).  Returns ``(plan, keep)``, ``keep`` the
+    bool [nnz] mask in COO order; ``p == 0`` returns the parent plan itself."""
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"drop_edges: p must be in [0, 1], got {p}")
+    if p == 0:
+        return plan, torch.ones(plan.nnz, dtype=torch.bool, device=plan.device)
+    keep = torch.rand(plan.nnz, device=plan.device, generator=generator) >= p
+    return plan.select_edges(keep), keep
+
+
+def _keep_mask(keep: torch.Tensor, nnz: int) -> torch.Tensor:
+    if keep.dtype != torch.bool or keep.dim() != 1 or keep.numel() != nnz:
+        raise ValueError(f"keep must be a bool [{nnz}] mask, got {keep.dtype} "
+                         f"{tuple(keep.shape)}")
+    return keep.contiguous()
+
+
+def _same_device(g: GraphPlan, t: torch.Tensor) -> None:
+    dev = L.require_device(t)
+    if dev != g.device:
+        raise L.MgcnError(f"tensor on {dev}, graph is on {g.device}")
+
+
+def _raise_bad_ids(flags, n: int) -> None:
+    out_of_range, repeated = (bool(f) for f in flags)
+    if out_of_range:
+        raise ValueError(f"induced: node id out of range (expected 0 <= id < {n})")
+    if repeated:
+        raise ValueError("induced: repeated node id")
+
+
+def _edge_rank(g: GraphPlan, keep: torch.Tensor | None, node_map: torch.Tensor | None):
+    """(eid_new int32 [nnz], total 0-d int64 on the device): libmgcn
+    ``mgcn_edge_rank`` -- the rank of every COO edge among the edges that are
+    kept and, with ``node_map``, have both endpoints mapped to >= 0."""
+    lib = L.load()
+    dev = g.device
+    nnz = g.nnz
+    eid_new = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
+    total = torch.zeros((), dtype=torch.int64, device=dev)
+    if nnz == 0:
+        return eid_new, total
+    ws_bytes = int(lib.mgcn_edge_rank_workspace_bytes(nnz))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    f, b = g.fwd, g.bwd  # the sources are fwd's columns, the destinations bwd's
+    with L.device_guard(dev):
+        rc = lib.mgcn_edge_rank(nnz, L.ptr(keep), L.ptr(f.col), L.ptr(f.eid), L.ptr(node_map),
+                                L.ptr(b.col), L.ptr(b.eid), L.ptr(node_map), L.ptr(eid_new),
+                                L.ptr(total), L.ptr(ws), ws_bytes, L.stream_of(dev))
+    L.check(rc, "mgcn_edge_rank")
+    return eid_new, total
+
+
+def derive_view(view: CSRView, eid_new: torch.Tensor, nnz_out: int, n_rows_out: int,
+                n_cols_out: int, col_map: torch.Tensor | None, row_src: torch.Tensor | None,
+                ws: torch.Tensor | None = None, schedule: bool = True) -> CSRView:
+    """The view of the surviving edges (libmgcn ``mgcn_csr_derive``): a stable
+    compaction of ``view``'s slots, rows ``row_src`` (None: all, in place),
+    columns renamed by ``col_map`` (None: kept)."""
+    lib = L.load()
+    dev = view.rowptr.device
+    rowptr = torch.empty(n_rows_out + 1, dtype=torch.int64, device=dev)
+    col = torch.empty(max(nnz_out, 1), dtype=torch.int32, device=dev)[:nnz_out]
+    eid = torch.empty(max(nnz_out, 1), dtype=torch.int32, device=dev)[:nnz_out]
+    ws_bytes = int(lib.mgcn_csr_derive_workspace_bytes(view.n_rows, n_rows_out, view.nnz))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if n_rows_out == 0:  # no row to fill (and no row_src array to point at)
+        rowptr.zero_()
+        return CSRView(rowptr=rowptr, col=col, eid=eid, n_rows=0, n_cols=n_cols_out)
+    with L.device_guard(dev):
+        rc = lib.mgcn_csr_derive(view.n_rows, view.n_cols, view.nnz, L.ptr(view.rowptr),
+                                 L.ptr(view.col), L.ptr(view.eid), L.ptr(row_src), n_rows_out,
+                                 L.ptr(col_map), L.ptr(eid_new), nnz_out, L.ptr(rowptr),
+                                 L.ptr(col), L.ptr(eid), L.ptr(ws), ws.numel(),
+                                 L.stream_of(dev))
+    L.check(rc, "mgcn_csr_derive")
+    out = CSRView(rowptr=rowptr, col=col, eid=eid, n_rows=n_rows_out, n_cols=n_cols_out)
+    return schedule_rows(out) if schedule else out
+
+
+def _derive(g: GraphPlan, eid_new: torch.Tensor, nnz_out: int, n_out: int,
+            node_map: torch.Tensor | None, row_src: torch.Tensor | None) -> GraphPlan:
+    """The child plan: both views derived, ``in_cnt`` and the row schedules as
+    :func:`build_plan` forms them; norms, slot_map and coo start empty."""
+    lib = L.load()
+    ws = torch.empty(int(lib.mgcn_csr_derive_workspace_bytes(g.num_nodes, n_out, g.nnz)),
+                     dtype=torch.uint8, device=g.device)
+    fwd = derive_view(g.fwd, eid_new, nnz_out, n_out, n_out, node_map, row_src, ws)
+    bwd = derive_view(g.bwd, eid_new, nnz_out, n_out, n_out, node_map, row_src, ws)
+    in_cnt = (fwd.rowptr[1:] - fwd.rowptr[:-1]).clamp_(min=1).to(torch.float32)
+    return GraphPlan(num_nodes=n_out, nnz=nnz_out, device=g.device, fwd=fwd, bwd=bwd,
+                     in_cnt=in_cnt)

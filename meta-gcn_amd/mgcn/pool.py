@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from torch.nn import Parameter
 
 from . import _lib as L
-from .graph import build_view
+from .graph import adopt_derived, build_view
 from .models import activation, glorot, zeros
 from .ops import bmm, scatter_, spmm_fwd
 from .pyg import GraphConv, remove_self_loops, uniform
@@ -109,6 +109,12 @@ def coalesce(edge_index: torch.Tensor, num_nodes: int) -> torch.Tensor:
 def filter_adj(edge_index, edge_attr, perm, num_nodes=None):
     """torch_geometric.nn.pool.topk_pool.filter_adj (PyG 1.3): keep edges
     whose endpoints are both in ``perm``, relabelled to positions in perm."""
+    return _filter_adj(edge_index, edge_attr, perm, num_nodes)[:2]
+
+
+def _filter_adj(edge_index, edge_attr, perm, num_nodes=None):
+    """:func:`filter_adj`, returning the bool [E] mask of the kept edges and
+    the node map (new id of every node, -1 outside ``perm``) as well."""
     if num_nodes is None:
         num_nodes = int(edge_index.max().item()) + 1 if edge_index.numel() else 0
     mask = perm.new_full((num_nodes,), -1)
@@ -118,7 +124,7 @@ def filter_adj(edge_index, edge_attr, perm, num_nodes=None):
     row, col = row[keep], col[keep]
     if edge_attr is not None:
         edge_attr = edge_attr[keep]
-    return torch.stack([row, col], dim=0), edge_attr
+    return torch.stack([row, col], dim=0), edge_attr, keep, mask
 
 
 def topk(x: torch.Tensor, ratio: float, batch: torch.Tensor, min_score=None, tol=1e-7):
@@ -188,7 +194,12 @@ def _select(x, edge_index, edge_attr, batch, score, ratio, min_score, multiplier
     x = x[perm] * score[perm].view(-1, 1)
     x = multiplier * x if multiplier != 1 else x
     batch = batch[perm]
-    edge_index, edge_attr = filter_adj(edge_index, edge_attr, perm, num_nodes=score.size(0))
+    parent = edge_index
+    edge_index, edge_attr, kept, node_map = _filter_adj(edge_index, edge_attr, perm,
+                                                        num_nodes=score.size(0))
+    # the next conv's plan: derived from this graph's (when it has one) rather
+    # than rebuilt from the new edge list (graph.set_derived_plans)
+    adopt_derived(parent, score.size(0), kept, edge_index, perm.size(0), perm, node_map)
     return x, edge_index, edge_attr, batch, perm, score[perm]
 
 

@@ -30,7 +30,7 @@ import torch.nn as nn
 from torch.nn import Parameter
 from torch.nn.utils.rnn import pad_sequence
 
-from .graph import plan_for
+from .graph import adopt_derived, plan_for
 from .models import Linear, activation, glorot, zeros
 from .ops import hard_attention_aggregate, linear
 from .pool import scatter_max_arg
@@ -52,6 +52,11 @@ def subgraph(subset, edge_index, edge_attr=None, relabel_nodes=False, num_nodes=
     """gpool_hard_attention.py:25-71 (torch_geometric.utils.subgraph with the
     masks on edge_index's device): the subgraph induced by ``subset`` (node
     ids, or a bool mask), optionally relabelled to consecutive ids."""
+    return _subgraph(subset, edge_index, edge_attr, relabel_nodes, num_nodes)[:2]
+
+
+def _subgraph(subset, edge_index, edge_attr=None, relabel_nodes=False, num_nodes=None):
+    """:func:`subgraph`, returning the bool [E] mask of the kept edges as well."""
     device = edge_index.device
     if isinstance(subset, (list, tuple)):
         subset = torch.tensor(subset, dtype=torch.long, device=device)
@@ -73,7 +78,7 @@ def subgraph(subset, edge_index, edge_attr=None, relabel_nodes=False, num_nodes=
     edge_attr = edge_attr[mask] if edge_attr is not None else None
     if relabel_nodes:
         edge_index = n_idx[edge_index]
-    return edge_index, edge_attr
+    return edge_index, edge_attr, mask
 
 
 def get_edge_select(x, edge_index, alpha, training=True, p_keep=None):
@@ -105,19 +110,25 @@ def prune(x, edge_index, edge_select, relabel=False, batch_slices_x=None):
     and returns, for every graph boundary, the number of kept nodes below it.
     Returns (x, edge_index, nodes (sorted), batch_slices_x)."""
     nodes = edge_index[1, edge_select].unique()
+    parent, n_parent = edge_index, x.size(0)
     if relabel:
         assert batch_slices_x is not None
-        edge_index, _ = subgraph(nodes, edge_index, relabel_nodes=True, num_nodes=x.size(0))
+        edge_index, _, kept = _subgraph(nodes, edge_index, relabel_nodes=True,
+                                        num_nodes=x.size(0))
         x = x[nodes, :]
         batch_slices_x_pruned = [0]
         for end in batch_slices_x[1:]:
             batch_slices_x_pruned.append(int((nodes < end).sum().item()))
     else:
-        edge_index, _ = subgraph(nodes, edge_index, relabel_nodes=False, num_nodes=x.size(0))
+        edge_index, _, kept = _subgraph(nodes, edge_index, relabel_nodes=False,
+                                        num_nodes=x.size(0))
         nodes_prune_mask = x.new_ones(x.size(0), dtype=torch.bool)
         nodes_prune_mask[nodes] = False
         x[nodes_prune_mask, :] = 0
         batch_slices_x_pruned = batch_slices_x
+    # the next layer's plan: derived from this graph's (when it has one) rather
+    # than rebuilt from the new edge list (graph.set_derived_plans)
+    adopt_derived(parent, n_parent, kept, edge_index, x.size(0), nodes if relabel else None)
     return x, edge_index, nodes, batch_slices_x_pruned
 
 
