@@ -295,6 +295,34 @@ int mgcn_relu_bwd_colsum_bf16(int64_t n_rows, int32_t F, const uint16_t *dZ,
                               void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Fused bf16 layer (addition to ABI 22, backward compatible): the aggregation
+ * of bf16 rows and a 128 x 128 bf16 product in one launch, for both
+ * directions of a layer.
+ *   Zf = reduce_k float(X[col_k]) * w_k [/ cnt[col_k]] [/ max(count, 1)] [* row_scale[row]]
+ *   Zb = bf16(Zf)                       (round to nearest even, once)
+ *   Y  = bf16(epi(float(Zb) @ float(B or B^T) + bias)),  epi = optional ReLU
+ * Zf is formed exactly as mgcn_spmm_fwd_bf16 / mgcn_spmm_bwd_bf16 form it, so
+ * Zb has their bits; the product is one bf16 MFMA term accumulated in fp32
+ * (every product exact) and Y is rounded once.  Deterministic.
+ * Forward: the fwd view, w = w_fwd, B = W, reduce = SUM or MEAN (division by
+ * max(count, 1)), bias / relu, Z (optional, [n_rows, 128]) receives Zb.
+ * Adjoint (dX): the bwd view, w = w_bwd, row_scale, reduce = SUM, and for a
+ * mean layer cnt (every gathered row divided by cnt[col], as
+ * mgcn_spmm_bwd_bf16's MEAN), B = W with transpose_b = 1.
+ * w, row_scale, cnt, bias and Z are NULL where unused.  Shapes: F_in = F_out
+ * = 128 (mgcn_spmm_xw_bf16_supported), every leading dimension >= 128 and
+ * % 8 == 0, X / B / Y / Z 16-byte aligned; cnt together with reduce != SUM,
+ * or anything else, is MGCN_EINVAL.  Every row is folded by one 16-lane
+ * group: meant for views without heavy rows.
+ */
+int mgcn_spmm_xw_bf16_supported(int32_t F_in, int32_t F_out, int reduce);
+int mgcn_spmm_xw_bf16(int64_t n_rows, int32_t F_in, int32_t F_out, const int64_t *rowptr,
+                      const int32_t *col, const float *w, const float *row_scale,
+                      const float *cnt, const uint16_t *X, int64_t ldx, const uint16_t *B,
+                      int64_t ldb, int transpose_b, const float *bias, int relu, uint16_t *Y,
+                      int64_t ldy, uint16_t *Z, int64_t ldz, int reduce, void *stream);
+
+/*
  * Row schedule (degree skew: the botnet graphs reach degree ~6k, config 3).
  * mgcn_row_schedule writes every row id into order[n_rows], by degree,
  * heaviest first (stable: equal degrees keep ascending ids), and returns

@@ -67,6 +67,9 @@ SIGNATURES = {
     "mgcn_spmm_bwd_bf16": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _int,
                                   _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "mgcn_relu_bwd_colsum_bf16": (_int, [_i64, _i32, _vp, _vp, _int, _vp, _vp, _vp, _sz, _vp]),
+    "mgcn_spmm_xw_bf16_supported": (_int, [_i32, _i32, _int]),
+    "mgcn_spmm_xw_bf16": (_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
+                                 _int, _vp, _int, _vp, _i64, _vp, _i64, _int, _vp]),
     "mgcn_slot_map_workspace_bytes": (_sz, [_i64]),
     "mgcn_slot_map": (_int, [_i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mgcn_max_mask": (_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -718,7 +718,7 @@ class GCNStack(nn.Module):
 
     def _fusable(self, x=None):
         if x is not None and x.dtype != torch.float32:
-            return None  # bf16 activations: layer by layer (no fused bf16 layer kernel)
+            return None  # bf16 activations: layer by layer through gcn_layer
         nms = []
         for layer in self.layers:
             g = layer.gcn

@@ -40,8 +40,10 @@ from .ops_attention import (_AttentionAggregate, _HardAttentionEval,  # noqa: F4
 from .ops_gate import _GateAggregate, gate_aggregate  # noqa: F401
 from .ops_multi import (_MultiAggregate, multi_aggregate, multi_kernel_fusable,  # noqa: F401
                         multi_kernel_reason, multi_spmm_bwd, multi_spmm_fwd)
-from .ops_bf16 import (ROW_COPIES, _AggregateBf16, _SegmentReduceBf16,  # noqa: F401
-                       relu_bwd_colsum_bf16, spmm_bf16_supported, spmm_bwd_bf16, spmm_fwd_bf16)
+from .ops_bf16 import (ROW_COPIES, _AggregateBf16, _LayerXWBf16, _SegmentReduceBf16,  # noqa: F401
+                       relu_bwd_colsum_bf16, spmm_bf16_supported, spmm_bwd_bf16, spmm_fwd_bf16,
+                       spmm_xw_bf16, spmm_xw_bf16_supported, spmm_xw_bwd_bf16,
+                       spmm_xw_fwd_bf16)
 from .ops_pack import (PACK_ROWS_WIDTHS, PackedTable, _SegmentMean, pack_rows,  # noqa: F401
                        pack_rows_count, pack_rows_values, packed_cols, packed_row_bits,
                        segment_mean, unpack_rows)
@@ -56,6 +58,12 @@ def __getattr__(name):
 # fused aggregate-then-transform forward for 128 -> 128 sum / mean layers
 # (mgcn_spmm_xw_fwd); MGCN_FUSE_XW=0 selects the GEMM + SpMM launches
 _FUSE_XW = os.environ.get("MGCN_FUSE_XW", "1") != "0"
+
+# fused bf16 layer (mgcn_spmm_xw_bf16: one launch per direction for a bf16
+# 128 -> 128 sum / mean layer).  Opt-in, MGCN_BF16_FUSED=1: it rounds the
+# aggregate Z = A x to bf16 where the two-launch route rounds h = x W, so a
+# layer's bits (and its error bound) change with the switch
+_BF16_FUSED = os.environ.get("MGCN_BF16_FUSED", "0") != "0"
 
 # one launch per direction for a multi-kernel layer (mgcn_multi_spmm_fwd /
 # _bwd, :func:`multi_kernel_fusable`); MGCN_FUSE_MULTI=0 keeps the loop over
@@ -77,6 +85,15 @@ def set_fused_layers(enabled: bool) -> None:
     kernels (mgcn_spmm_xw_fwd / _bwd) where they apply."""
     global _FUSE_XW
     _FUSE_XW = bool(enabled)
+
+
+def set_bf16_fused_layers(enabled: bool) -> None:
+    """Send (True) a bf16 128 -> 128 sum / mean layer of :func:`gcn_layer`
+    through the fused bf16 kernel (mgcn_spmm_xw_bf16), or keep (False, the
+    default; env MGCN_BF16_FUSED=1 turns it on) the vendor GEMM followed by
+    the bf16 aggregation."""
+    global _BF16_FUSED
+    _BF16_FUSED = bool(enabled)
 
 
 def set_fused_multi_kernel(enabled: bool) -> None:
@@ -174,6 +191,17 @@ def layer_fusable(plan: GraphPlan, x: torch.Tensor, W: torch.Tensor, reduce: int
             x.is_cuda and x.size(0) == plan.fwd.n_cols == plan.fwd.n_rows and
             spmm_xw_supported(plan.fwd, W.size(0), W.size(1), reduce, x.stride(0)) and
             spmm_xw_supported(plan.bwd, W.size(1), W.size(0), L.REDUCE_SUM))
+
+
+def layer_fusable_bf16(plan: GraphPlan, x: torch.Tensor, W: torch.Tensor, reduce: int) -> bool:
+    """Both directions of a bf16 layer on ``plan`` fit the fused bf16 kernel
+    (:func:`spmm_xw_bf16_supported`: 128 -> 128, sum / mean, no heavy rows in
+    either view)."""
+    return (x.dim() == 2 and x.dtype == torch.bfloat16 and W.dtype == torch.bfloat16 and
+            W.dim() == 2 and x.is_cuda and
+            x.size(0) == plan.fwd.n_cols == plan.fwd.n_rows and x.size(1) == W.size(0) and
+            spmm_xw_bf16_supported(plan.fwd, W.size(0), W.size(1), reduce) and
+            spmm_xw_bf16_supported(plan.bwd, W.size(1), W.size(0), L.REDUCE_SUM))
 
 
 def spmm_xw_fwd(view: CSRView, w: torch.Tensor | None, X: torch.Tensor, W: torch.Tensor,
@@ -597,7 +625,10 @@ def gcn_layer(x: torch.Tensor, W: torch.Tensor, plan: GraphPlan, norm: NormPlan,
     view, gathered tables within 4 GiB); otherwise the GEMM and the
     aggregation run as separate launches, in the order the caller's
     reference uses: ``aggregate_first`` (PyG SAGEConv: mean_j x_j, then
-    @ W + b) or x @ W first (the default)."""
+    @ W + b) or x @ W first (the default).  A bfloat16 ``x`` takes the two
+    launches unless :func:`set_bf16_fused_layers` is on and
+    :func:`layer_fusable_bf16` holds: then one mgcn_spmm_xw_bf16 launch per
+    direction (:class:`_LayerXWBf16`)."""
     reduce = L.REDUCE_CODES[aggr]
     if x.dtype == torch.bfloat16 and W.dtype != x.dtype:
         # fp32 master weights under bf16 activations: the cast is an autograd
@@ -606,6 +637,8 @@ def gcn_layer(x: torch.Tensor, W: torch.Tensor, plan: GraphPlan, norm: NormPlan,
         W = W.to(x.dtype)
     if _FUSE_XW and not norm.grad and layer_fusable(plan, x, W, reduce):
         return _LayerXW.apply(x, W, bias, plan, norm, reduce, bool(relu))
+    if _BF16_FUSED and not norm.grad and layer_fusable_bf16(plan, x, W, reduce):
+        return _LayerXWBf16.apply(x, W, bias, plan, norm, reduce, bool(relu))
     if aggregate_first:
         out = linear(aggregate_plan(x, plan, norm, aggr), W)
         if bias is not None:

@@ -11,7 +11,12 @@ rounded once, to nearest even, at the store.  The result is bit for bit the
 fp32 path on the upcast input, rounded to bf16; so every case the kernels do
 not take (``F % 8 != 0``, a differentiable norm, a 1-D ``scatter_``) goes
 through upcast -> fp32 path -> round in :mod:`mgcn.ops` and gives the same
-bits."""
+bits.
+
+The fused bf16 layer (``mgcn_spmm_xw_bf16``, :class:`_LayerXWBf16`) lives here
+too: the same aggregate, rounded to bf16 once and multiplied by a 128 x 128
+bf16 matrix on one MFMA term in the same launch.  :func:`mgcn.ops.gcn_layer`
+takes it only behind :func:`mgcn.ops.set_bf16_fused_layers`."""
 from __future__ import annotations
 
 from collections import Counter
@@ -165,6 +170,108 @@ class _AggregateBf16(torch.autograd.Function):
         if db is not None and db.dtype != ctx.bias_dtype:
             db = db.to(ctx.bias_dtype)  # a bf16 bias parameter: its gradient rounded once
         return dH, db, None, None, None, None
+
+
+def spmm_xw_bf16_supported(view: CSRView, F_in: int, F_out: int, reduce: int,
+                           ld: int | None = None) -> bool:
+    """True when :func:`spmm_xw_fwd_bf16` (``view`` the fwd view) or
+    :func:`spmm_xw_bwd_bf16` (``view`` the bwd view, F_in / F_out swapped)
+    takes this layer: 128 -> 128, sum or mean, no heavy rows, and -- when
+    given -- a leading dimension ``ld`` of the gathered rows that keeps them
+    16-byte aligned in place."""
+    if ld is not None and (int(ld) < int(F_in) or int(ld) % 8):
+        return False
+    return (view.n_heavy == 0 and view.n_cols > 0 and
+            bool(L.load().mgcn_spmm_xw_bf16_supported(int(F_in), int(F_out), int(reduce))))
+
+
+def spmm_xw_bf16(view: CSRView, w, row_scale, cnt, X: torch.Tensor, W: torch.Tensor,
+                 transpose: bool, bias, relu: bool, reduce: int, want_z: bool,
+                 tname: str | None = "spmm_xw_bf16"):
+    """``mgcn_spmm_xw_bf16`` as it stands, both directions: (Y, Zb or None) with
+    Y = round(epi(Zb @ (W^T if transpose else W) + bias)); the launch is
+    timed under ``tname``.  :func:`spmm_xw_fwd_bf16` and
+    :func:`spmm_xw_bwd_bf16` are the two uses a layer makes of it."""
+    lib = L.load()
+    X = _rows_bf16(X, "X" if not transpose else "dY")
+    W = _rows_bf16(W, "W")
+    dev = L.require_device(X, W, view.rowptr, w, row_scale, cnt, bias)
+    if X.size(0) != view.n_cols:
+        raise ValueError(f"gathered table has {X.size(0)} rows, the view has {view.n_cols} columns")
+    if X.size(1) != 128 or tuple(W.shape) != (128, 128) or view.n_heavy:
+        raise ValueError("the fused bf16 layer kernel takes 128 -> 128 layers on views without "
+                         f"heavy rows: X {tuple(X.shape)}, W {tuple(W.shape)}, "
+                         f"n_heavy = {view.n_heavy}")
+    Y = torch.empty(view.n_rows, 128, dtype=BF16, device=dev)
+    Z = torch.empty(view.n_rows, 128, dtype=BF16, device=dev) if want_z else None
+    bias = _bias_f32(bias, 128)
+    launch(tname, "mgcn_spmm_xw_bf16", dev, view.n_rows, view.edges, lib.mgcn_spmm_xw_bf16,
+           view.n_rows, 128, 128, L.ptr(view.rowptr), L.ptr(view.col), L.ptr(w),
+           L.ptr(row_scale), L.ptr(cnt), L.ptr(X), X.stride(0), L.ptr(W), W.stride(0),
+           int(bool(transpose)), L.ptr(bias), int(bool(relu)), L.ptr(Y), Y.stride(0), L.ptr(Z),
+           128, reduce, L.stream_of(dev))
+    return Y, Z
+
+
+def spmm_xw_fwd_bf16(view: CSRView, w: torch.Tensor | None, X: torch.Tensor, W: torch.Tensor,
+                     reduce: int, bias: torch.Tensor | None = None, relu: bool = False,
+                     want_z: bool = False):
+    """Y (bf16) = round(epi(Zb @ W + bias)), Zb = :func:`spmm_fwd_bf16`'s rows
+    bit for bit (for mean the divided rows), in one launch
+    (``mgcn_spmm_xw_bf16``): bf16 ``X`` [n_cols, 128] and ``W`` [128, 128],
+    fp32 weights and bias, one bf16 MFMA term with fp32 accumulators.  With
+    ``want_z`` returns (Y, Zb)."""
+    if reduce not in (L.REDUCE_SUM, L.REDUCE_MEAN):
+        raise ValueError("spmm_xw_fwd_bf16: sum or mean only (max does not commute with W)")
+    Y, Z = spmm_xw_bf16(view, w, None, None, X, W, False, bias, relu, reduce, want_z,
+                        tname="spmm_xw_fwd_z_bf16" if want_z else "spmm_xw_fwd_bf16")
+    return (Y, Z) if want_z else Y
+
+
+def spmm_xw_bwd_bf16(view_t: CSRView, w_t: torch.Tensor | None, row_scale: torch.Tensor | None,
+                     dY: torch.Tensor, W: torch.Tensor, cnt: torch.Tensor | None = None):
+    """dX (bf16) = round(dHb @ W^T), dHb = :func:`spmm_bwd_bf16`'s rows bit
+    for bit (sum, or mean when ``cnt`` is given: every gathered dY row divided
+    by cnt inside the kernel), in one launch (``mgcn_spmm_xw_bf16`` with the
+    transpose flag)."""
+    return spmm_xw_bf16(view_t, w_t, row_scale, cnt, dY, W, True, None, False, L.REDUCE_SUM, False,
+                        tname="spmm_xw_bwd_bf16")[0]
+
+
+class _LayerXWBf16(torch.autograd.Function):
+    """One bf16 GCN layer  y = epi((A_norm x) W + b)  on the fused bf16 kernel:
+    the forward is one launch (Z = the rounded aggregate kept only when W
+    wants a gradient); the backward runs relu_bwd_colsum_bf16 (dY, fp32 db),
+    dW = Z^T dY on the vendor bf16 GEMM and one spmm_xw_bwd_bf16 for dx."""
+
+    @staticmethod
+    def forward(ctx, x, W, bias, plan: GraphPlan, norm: NormPlan, reduce: int, relu: bool):
+        want_z = bool(ctx.needs_input_grad[1])
+        out = spmm_xw_fwd_bf16(plan.fwd, norm.w_fwd, x, W, reduce, bias, relu, want_z=want_z)
+        Y, Z = out if want_z else (out, None)
+        ctx.plan, ctx.norm, ctx.reduce, ctx.relu = plan, norm, reduce, relu
+        ctx.bias_dtype = bias.dtype if bias is not None else None
+        ctx.save_for_backward(W, Y if relu else None, Z)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dZ):
+        W, Y, Z = ctx.saved_tensors
+        plan, norm = ctx.plan, ctx.norm
+        need_b = ctx.bias_dtype is not None and ctx.needs_input_grad[2]
+        mean = ctx.reduce == L.REDUCE_MEAN
+        dY, db = relu_bwd_colsum_bf16(dZ.to(BF16), Y, ctx.relu, need_b)
+        dW = dx = None
+        if Z is not None:
+            from .ops_gemm import VENDOR_GEMMS
+            VENDOR_GEMMS[("matmul", (Z.size(1), Z.size(0)), tuple(dY.shape), str(BF16))] += 1
+            dW = torch.matmul(Z.t(), dY)  # mean: Z is the divided row, dY undivided
+        if ctx.needs_input_grad[0]:
+            dx = spmm_xw_bwd_bf16(plan.bwd, norm.w_bwd, norm.row_scale_bwd, dY, W,
+                                  cnt=plan.in_cnt if mean else None)
+        if db is not None and db.dtype != ctx.bias_dtype:
+            db = db.to(ctx.bias_dtype)
+        return dx, dW, db, None, None, None, None
 
 
 class _SegmentReduceBf16(torch.autograd.Function):
