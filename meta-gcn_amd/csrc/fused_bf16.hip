@@ -22,7 +22,7 @@
 //   3. One rounding at the store of Y; no atomics, a fixed chunk -> workgroup
 //      map: deterministic from run to run.
 //
-// Work split (fused.hip's plain chunk kernel): persistent 512-thread
+// Work split (fused_fwd.hip's plain chunk kernel): persistent 512-thread
 // workgroups, two per CU; chunk c (rows 32 c .. 32 c + 31) goes to workgroup
 // c % grid.
 //   Phase A (gather, spmm_bf16_kernel at G = 16): row 4 wave + grp of the
@@ -305,11 +305,7 @@ __global__ __launch_bounds__(kThreads, 2 * kPerCU) void spmm_xw_bf16_kernel(cons
 }
 
 int grid_size(int64_t n_chunks) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    cus = 256;
-  const int64_t g = (int64_t)kPerCU * cus;
+  const int64_t g = (int64_t)kPerCU * device_cus();
   return (int)(g < n_chunks ? g : n_chunks);
 }
 

@@ -7,7 +7,7 @@
 //
 // The reference computes a layer as x @ W then gather -> * norm ->
 // scatter_add (src/gcn_meta/models/gcn_base_models.py:201, 223-237); the
-// association and the numerics follow fused.hip's F = 128 kernels (the
+// association and the numerics follow xw128.h's F = 128 kernels (the
 // aggregation bit for bit the SpMM's, the dense product bf16x6), but the
 // shapes of a 256-wide layer change three things:
 //
@@ -50,60 +50,14 @@
 // and 24 KB of L2-resident W fragments per row ride under the gathers.
 
 #include "mgcn_internal.h"
+#include "ws_handoff.h"
 #include "x6.h"
 
 namespace mgcn {
 
-// mgcn_set_option("wide_pair"): both rows of a wave's pair gathered together
-// or one after the other -- bit 0 the forward, bit 1 the adjoint (default 3:
-// both paired).  Gathered rows in flight per row and round: 4 (5 / 6 / 8
-// measured slower, round 5, and removed)
-int g_wide_pair = 3;
+// Gathered rows in flight per row and round: 4 (5 / 6 / 8 measured slower,
+// round 5, and removed)
 constexpr int kWideU = 4;
-// mgcn_set_option("wide_ws"): the warp-specialised kernels (below) -- bit 0
-// the forward, bit 1 the adjoint
-int g_wide_ws = 3;
-// mgcn_set_option("wide_dbg"): timing experiments on the warp-specialised
-// kernels (results are WRONG when set): bit 0 the MFMA waves skip their W
-// loads, bit 1 they skip the products, bit 2 the gather waves skip the gathers;
-// bits 3 / 4: s_setprio 2 on the gather / MFMA waves (results stay exact)
-int g_wide_dbg = 0;
-// mgcn_set_option("wide_mfma"): MFMA waves of the warp-specialised kernels (4 or 8)
-int g_wide_mfma = 8;
-
-int wide_set_option(const char *name, int value) {
-  if (name[5] == 'm') {
-    if (value != 4 && value != 8) {
-      set_error("wide_mfma must be 4 or 8");
-      return MGCN_EINVAL;
-    }
-    g_wide_mfma = value;
-    return MGCN_OK;
-  }
-  if (name[5] == 'd') {  // (timing experiments: results WRONG when set)
-    if (!MGCN_EXPERIMENT) {
-      set_error("wide_dbg: experiment builds only (make exp -> libmgcn_exp.so)");
-      return MGCN_EINVAL;
-    }
-    g_wide_dbg = value;
-    return MGCN_OK;
-  }
-  if (name[5] == 'w') {
-    if (value < 0 || value > 3) {
-      set_error("wide_ws must be 0 .. 3");
-      return MGCN_EINVAL;
-    }
-    g_wide_ws = value;
-    return MGCN_OK;
-  }
-  if (value < 0 || value > 3) {  // "wide_pair"
-    set_error("wide_pair must be 0 .. 3");
-    return MGCN_EINVAL;
-  }
-  g_wide_pair = value;
-  return MGCN_OK;
-}
-
 namespace {
 
 using namespace x6;
@@ -124,7 +78,7 @@ constexpr int kWImgFrags = kWKs * kWNt * 3 * 64;  // 16-B fragments of the W ima
 constexpr int kWMaskWords = 8;                    // mask words per row
 
 constexpr int WEPI_STORE = 0, WEPI_RELU = 1, WEPI_RELU_DIV = 2;
-// Y / Z rows leave with the nt cache policy, as in fused.hip (a 51-GB table
+// Y / Z rows leave with the nt cache policy, as in xw128.h (a 51-GB table
 // never stays in the Infinity Cache anyway)
 constexpr int kWideNt = 2;
 
@@ -180,7 +134,7 @@ struct WideArgs {
   float *colsum_partial;       // backward: [grid][256]
   int mean, relu;
   int dbg;                     // wide_dbg (experiment builds only; masked by kDbgMask)
-  uint32_t spin;               // warp-specialised hand-off spin bound (g_spin_limit)
+  uint32_t spin;               // warp-specialised hand-off spin bound ("ws_spin_limit")
   unsigned *err;               // device error word: kDevErrWide when a hand-off gave up
   // packed table (mgcn_packed_table; the warp-specialised kernels, PK): X is
   // then unused and col holds (segment << pk_rbits) | row
@@ -253,10 +207,7 @@ __device__ __forceinline__ void wide_gather(const float *__restrict__ X, int64_t
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (k0 + u < nb) {  // wave-uniform: strictly ascending edge order
-          acc[0] = __fadd_rn(acc[0], __fmul_rn(xv[u].x, wk[u]));
-          acc[1] = __fadd_rn(acc[1], __fmul_rn(xv[u].y, wk[u]));
-          acc[2] = __fadd_rn(acc[2], __fmul_rn(xv[u].z, wk[u]));
-          acc[3] = __fadd_rn(acc[3], __fmul_rn(xv[u].w, wk[u]));
+          fold4(acc, xv[u], wk[u]);
         }
       }
     }
@@ -318,16 +269,10 @@ __device__ __forceinline__ void wide_gather2(const float *__restrict__ X, int64_
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (k0 + u < na) {  // wave-uniform: strictly ascending edge order per row
-          aa[0] = __fadd_rn(aa[0], __fmul_rn(xa[u].x, wa[u]));
-          aa[1] = __fadd_rn(aa[1], __fmul_rn(xa[u].y, wa[u]));
-          aa[2] = __fadd_rn(aa[2], __fmul_rn(xa[u].z, wa[u]));
-          aa[3] = __fadd_rn(aa[3], __fmul_rn(xa[u].w, wa[u]));
+          fold4(aa, xa[u], wa[u]);
         }
         if (k0 + u < nb) {
-          ab[0] = __fadd_rn(ab[0], __fmul_rn(xb[u].x, wb[u]));
-          ab[1] = __fadd_rn(ab[1], __fmul_rn(xb[u].y, wb[u]));
-          ab[2] = __fadd_rn(ab[2], __fmul_rn(xb[u].z, wb[u]));
-          ab[3] = __fadd_rn(ab[3], __fmul_rn(xb[u].w, wb[u]));
+          fold4(ab, xb[u], wb[u]);
         }
       }
     }
@@ -496,17 +441,11 @@ __device__ __forceinline__ void wide_gather2_pk(const PkView &pv, const int32_t 
       for (int u = 0; u < U; ++u) {
         if (k0 + u < na) {  // wave-uniform: strictly ascending edge order per row
           const float4 x = pk_expand(nia[u], va[u]);
-          aa[0] = __fadd_rn(aa[0], __fmul_rn(x.x, wa[u]));
-          aa[1] = __fadd_rn(aa[1], __fmul_rn(x.y, wa[u]));
-          aa[2] = __fadd_rn(aa[2], __fmul_rn(x.z, wa[u]));
-          aa[3] = __fadd_rn(aa[3], __fmul_rn(x.w, wa[u]));
+          fold4(aa, x, wa[u]);
         }
         if (k0 + u < nb) {
           const float4 x = pk_expand(nib_b[u], vb[u]);
-          ab[0] = __fadd_rn(ab[0], __fmul_rn(x.x, wb[u]));
-          ab[1] = __fadd_rn(ab[1], __fmul_rn(x.y, wb[u]));
-          ab[2] = __fadd_rn(ab[2], __fmul_rn(x.z, wb[u]));
-          ab[3] = __fadd_rn(ab[3], __fmul_rn(x.w, wb[u]));
+          fold4(ab, x, wb[u]);
         }
       }
     }
@@ -788,7 +727,7 @@ __global__ __launch_bounds__(kWThreads, 4) void spmm_xw_wide_kernel(const WideAr
 // Hand-offs are LDS counters inside the workgroup (monotonic per buffer; a
 // wave's LDS operations complete in order, so its image writes land before
 // its counter add), polled with s_sleep and bounded: a spin that exceeds
-// the bound (g_spin_limit) sets the abort word and every wave leaves its loop.  The MFMA
+// the bound ("ws_spin_limit") sets the abort word and every wave leaves its loop.  The MFMA
 // term order is the 16-row kernel's with the operands swapped (the same six
 // products per k-step in the same order), so Y / dX equal its results.
 constexpr int kSRows = 32;
@@ -815,35 +754,6 @@ __device__ __forceinline__ f32x4_t mfma16_x6_wt(const u32x4 (&w)[3], const bf16x
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xm, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, xh, c, 0, 0, 0);
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int lds_load(const int *p) {
-  return __builtin_amdgcn_readfirstlane(
-      __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-}
-
-// wait until *p >= target (false: the abort word is set, leave)
-__device__ __forceinline__ bool lds_wait_ge(const int *p, int target, int *abort_word,
-                                            uint32_t limit) {
-  for (uint32_t n = 0;; ++n) {
-    if (lds_load(p) >= target) break;
-    if (lds_load(abort_word) != 0) return false;
-    if (n >= limit) {
-      __hip_atomic_store(abort_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      return false;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  asm volatile("" ::: "memory");
-  return true;
-}
-
-// this wave's LDS writes complete, then lane 0 adds v to *p; returns the old value
-__device__ __forceinline__ int lds_signal(int *p, int v, int lane) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  int old = 0;
-  if (lane == 0) old = __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  return __builtin_amdgcn_readfirstlane(old);
 }
 
 template <int U, bool BWD, int EPI, int NM, bool PK>
@@ -1171,18 +1081,11 @@ int launch_wide_ws_un(const WideArgs &a, bool bwd, int epi, int grid, hipStream_
 
 template <int U>
 int launch_wide_ws_u(const WideArgs &a, bool bwd, int epi, int grid, hipStream_t s) {
-  return g_wide_mfma == 8 ? launch_wide_ws_un<U, 8>(a, bwd, epi, grid, s)
+  return g_opt.wide_mfma == 8 ? launch_wide_ws_un<U, 8>(a, bwd, epi, grid, s)
                           : launch_wide_ws_un<U, 4>(a, bwd, epi, grid, s);
 }
 
-int wide_cus() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    cus = 256;
-  return cus;
-}
-int wide_grid() { return 2 * wide_cus(); }  // the two-phase kernels: two workgroups per CU
+int wide_grid() { return 2 * device_cus(); }  // the two-phase kernels: two workgroups per CU
 // The warp-specialised kernels hold one workgroup per CU at a time (their LDS),
 // over a grid of kWideWsGridMult x CUs: the hardware hands the next workgroup
 // to whichever CU frees first, so a CU slowed by work beside it -- a rank's
@@ -1191,7 +1094,7 @@ int wide_grid() { return 2 * wide_cus(); }  // the two-phase kernels: two workgr
 // stand-in for the receive writes: 183.8 -> 154.9 ms/step, 4 / 16 / 32 x:
 // 162.5 / 155.7 / 156.7; alone 119.4 vs 120.1 ms, profiles/r06/recv_load_ab.json)
 constexpr int kWideWsGridMult = 8;
-int wide_ws_grid() { return kWideWsGridMult * wide_cus(); }
+int wide_ws_grid() { return kWideWsGridMult * device_cus(); }
 
 template <int U, bool PAIR>
 int launch_wide_p(const WideArgs &a, bool bwd, int epi, int grid, hipStream_t s) {
@@ -1214,7 +1117,7 @@ int launch_wide_legacy(const WideArgs &a, bool bwd, int epi, int grid, hipStream
 
 // *grid: the workgroups launched (= the column-sum partials written)
 int launch_wide(const WideArgs &a, bool bwd, int epi, int *grid, hipStream_t s) {
-  if (a.pk != nullptr || (g_wide_ws & (bwd ? 2 : 1))) {  // (packed tables: this form only)
+  if (a.pk != nullptr || (g_opt.wide_ws & (bwd ? 2 : 1))) {  // (packed tables: this form only)
     const int64_t n_chunks = (a.n_rows + kSRows - 1) / kSRows;
     const int64_t g = wide_ws_grid();  // one workgroup per CU resident at a time
     *grid = (int)(g < n_chunks ? g : n_chunks);
@@ -1227,7 +1130,7 @@ int launch_wide(const WideArgs &a, bool bwd, int epi, int *grid, hipStream_t s) 
 }
 
 int launch_wide_legacy(const WideArgs &a, bool bwd, int epi, int grid, hipStream_t s) {
-  if (g_wide_pair & (bwd ? 2 : 1)) return launch_wide_p<kWideU, true>(a, bwd, epi, grid, s);
+  if (g_opt.wide_pair & (bwd ? 2 : 1)) return launch_wide_p<kWideU, true>(a, bwd, epi, grid, s);
   return launch_wide_p<kWideU, false>(a, bwd, epi, grid, s);
 }
 
@@ -1282,8 +1185,8 @@ int xw_wide_fwd(int64_t n_rows, const int64_t *rowptr, const int32_t *col, const
   a.ldz = ldz;
   a.mean = mean;
   a.relu = relu;
-  a.dbg = g_wide_dbg;
-  a.spin = g_spin_limit;
+  a.dbg = g_opt.wide_dbg;
+  a.spin = (uint32_t)g_opt.ws_spin_limit;
   a.err = device_error_word();
   if (a.err == nullptr) return MGCN_EHIP;
   set_packed(a, pk);
@@ -1316,8 +1219,8 @@ int xw_wide_bwd_dx(int64_t n_rows, const int64_t *rowptr_t, const int32_t *col_t
   a.mask_in = relu_mask;
   a.row_div = row_div;
   a.colsum_partial = partial;
-  a.dbg = g_wide_dbg;
-  a.spin = g_spin_limit;
+  a.dbg = g_opt.wide_dbg;
+  a.spin = (uint32_t)g_opt.ws_spin_limit;
   a.err = device_error_word();
   if (a.err == nullptr) return MGCN_EHIP;
   set_packed(a, pk);

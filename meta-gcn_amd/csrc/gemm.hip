@@ -22,7 +22,7 @@
 #include "x6.h"
 #include "tn_staged.h"
 
-// cache policy of gemm_bwd's X / Z rows (streamed once): 2 = nt (fused.hip)
+// cache policy of gemm_bwd's X / Z rows (streamed once): 2 = nt (xw128.h)
 #ifndef MGCN_NT_AUX
 #define MGCN_NT_AUX 2
 #endif
@@ -143,8 +143,7 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 // accumulator.  Dropped terms (ml, lm, ll) are below 2^-27 of |a b|; the
 // accumulator takes 6 K / 16 roundings per output against K for the f32
 // form.  Error vs fp64: scripts/bench_gemm.py, tests/test_gpu_parity.py.
-constexpr int PREC_F32 = 0, PREC_BF16X6 = 1;
-int g_gemm_precision = PREC_BF16X6;
+constexpr int PREC_F32 = 0, PREC_BF16X6 = 1;  // g_opt.gemm_precision
 
 
 // dW for M, N multiples of 128 in bf16x6.  Per chunk of 16 k-rows, each
@@ -641,25 +640,21 @@ bool tn_wide_fits(int64_t kps, int64_t lda, int64_t ldb) {
 
 bool tn_lds(int M, int N) { return M % kTile == 0 && N % kTile == 0; }
 
-// LDS-staged dW variants (mgcn_set_option "gemm_tn_variant"; measured at
-// K = 1M, M = N = 128: 0.321 / 0.335 / 0.337 ms): 0 = BK 64, one workgroup
-// per CU; 1 = BK 32, two; 2 = BK 16, three
-int g_tn_lds_variant = 0;
-int g_tn_staged = 1;  // M = 32, N = 32 / 64: gemm_tn_staged_kernel (0: gemm_tn_small_kernel)
-int tn_lds_wgs() { return g_tn_lds_variant == 1 ? 2 : g_tn_lds_variant == 2 ? 3 : 1; }
+// workgroups per CU of the LDS-staged dW variant ("gemm_tn_variant")
+int tn_lds_wgs() { return g_opt.gemm_tn_variant == 1 ? 2 : g_opt.gemm_tn_variant == 2 ? 3 : 1; }
 
 int gemm_splits(int64_t K, int M, int N) {
   // one resident round: 256 CUs x 3 workgroups (3 waves/SIMD at 134 VGPRs),
   // or x 2 for the LDS-staged kernel (64 KB of LDS each); at least 64 rows of
   // K per split (partials: splits x 64 KB per tile).  256 x 256 bf16x6
   // (gemm_tn_x6_wide_kernel): one workgroup per CU
-  if (tn_wide(M, N) && g_gemm_precision == PREC_BF16X6) {
+  if (tn_wide(M, N) && g_opt.gemm_precision == PREC_BF16X6) {
     int64_t s = 256, max_s = (K + 63) / 64;
     if (s > max_s) s = max_s;
     return (int)(s < 1 ? 1 : s);
   }
   const int tiles = ((M + kTile - 1) / kTile) * ((N + kTile - 1) / kTile);
-  const int per_cu = !tn_lds(M, N) ? 3 : g_gemm_precision == PREC_BF16X6 ? 3 : tn_lds_wgs();
+  const int per_cu = !tn_lds(M, N) ? 3 : g_opt.gemm_precision == PREC_BF16X6 ? 3 : tn_lds_wgs();
   int64_t s = 256 * per_cu / (tiles > 0 ? tiles : 1);
   int64_t max_s = (K + 63) / 64;
   if (s > max_s) s = max_s;
@@ -668,18 +663,6 @@ int gemm_splits(int64_t K, int M, int N) {
 }
 
 }  // namespace
-
-int gemm_set_tn_variant(int value) {
-  if (value < 0 || value > 2) return MGCN_EINVAL;
-  g_tn_lds_variant = value;
-  return MGCN_OK;
-}
-
-int gemm_set_tn_staged(int value) {
-  if (value < 0 || value > 1) return MGCN_EINVAL;
-  g_tn_staged = value;
-  return MGCN_OK;
-}
 
 }  // namespace mgcn
 
@@ -749,16 +732,16 @@ int gemm_tn_core(int64_t K, int32_t M, int32_t N, const float *A, int64_t lda, c
              reinterpret_cast<uintptr_t>(B) % 16 == 0 && lda % 4 == 0 && ldb % 4 == 0) {
     // 1-D grids of tiles x splits in the kernels' XCD-aware order
     const dim3 grid(tiles_m * tiles_n * used);
-    if (g_gemm_precision == PREC_BF16X6 && tn_wide(M, N) && tn_wide_fits(kps, lda, ldb))
+    if (g_opt.gemm_precision == PREC_BF16X6 && tn_wide(M, N) && tn_wide_fits(kps, lda, ldb))
       hipLaunchKernelGGL(gemm_tn_x6_wide_kernel, dim3(used), dim3(512), 0, s, A, lda, B, ldb, K,
                          kps, partial);
-    else if (g_gemm_precision == PREC_BF16X6)
+    else if (g_opt.gemm_precision == PREC_BF16X6)
       hipLaunchKernelGGL(gemm_tn_x6_kernel, grid, dim3(256), 0, s, A, lda, B, ldb, K, M, N, kps,
                          tiles_n, partial);
-    else if (g_tn_lds_variant == 1)
+    else if (g_opt.gemm_tn_variant == 1)
       hipLaunchKernelGGL((gemm_tn_lds_kernel<32, 2>), grid, dim3(256), 0, s, A, lda, B, ldb, K, M,
                          N, kps, tiles_n, partial);
-    else if (g_tn_lds_variant == 2)
+    else if (g_opt.gemm_tn_variant == 2)
       hipLaunchKernelGGL((gemm_tn_lds_kernel<16, 3>), grid, dim3(256), 0, s, A, lda, B, ldb, K, M,
                          N, kps, tiles_n, partial);
     else
@@ -1271,7 +1254,7 @@ template <int K>
 int launch_nn(int64_t M, int N, const float *A, int64_t lda, const float *B, int64_t sbk,
               int64_t sbn, float *C, int64_t ldc, int epi, const uint32_t *Z,
               const float *rd, float *partial, int *grid_out, hipStream_t s) {
-  if (g_gemm_precision == PREC_BF16X6)
+  if (g_opt.gemm_precision == PREC_BF16X6)
     return launch_nn_p<K, PREC_BF16X6>(M, N, A, lda, B, sbk, sbn, C, ldc, epi, Z, rd, partial,
                                        grid_out, s);
   return launch_nn_p<K, PREC_F32>(M, N, A, lda, B, sbk, sbn, C, ldc, epi, Z, rd, partial,
@@ -1394,7 +1377,7 @@ __global__ __launch_bounds__(kGenThreads) void gemm_gen_kernel(
 int launch_gen(int64_t M, int K, int N, const float *A, int64_t lda, const float *B, int64_t sbk,
                int64_t sbn, float *C, int64_t ldc, hipStream_t s) {
   const dim3 grid((unsigned)((M + kGenT - 1) / kGenT), (unsigned)((N + kGenT - 1) / kGenT));
-  if (g_gemm_precision == PREC_BF16X6)
+  if (g_opt.gemm_precision == PREC_BF16X6)
     hipLaunchKernelGGL(gemm_gen_kernel<PREC_BF16X6>, grid, dim3(kGenThreads), 0, s, A, lda, B, sbk,
                        sbn, C, ldc, M, K, N);
   else
@@ -1442,7 +1425,7 @@ __global__ __launch_bounds__(256) void fold_partials_kernel(const float *__restr
 }  // namespace
 
 // launchers of the split-K / column-sum folds, also for other translation
-// units (fused.hip's backward and elementwise.hip write the same partial slabs)
+// units (fused_bwd.hip's backward and elementwise.hip write the same partial slabs)
 int launch_fold(const float *partial, int64_t splits, int64_t MN, int N, float *C, int64_t ldc,
                 int accumulate, hipStream_t s) {
   return launch_fold_split(partial, splits, MN, N, C, ldc, N, nullptr, 0, accumulate, s);
@@ -1496,13 +1479,7 @@ int launch_colsum_fold(const float *partial, int64_t nparts, int N, float *out, 
   return launch_fold(partial, nparts, N, N, out, N, 0, s);
 }
 
-int gemm_precision_is_x6() { return g_gemm_precision == PREC_BF16X6; }
-
-int gemm_set_precision(int value) {
-  if (value != PREC_F32 && value != PREC_BF16X6) return MGCN_EINVAL;
-  g_gemm_precision = value;
-  return MGCN_OK;
-}
+int gemm_precision_is_x6() { return g_opt.gemm_precision == PREC_BF16X6; }
 
 }  // namespace mgcn
 
@@ -1922,7 +1899,7 @@ int launch_bwd(int grid, const float *X, int64_t ldx, const float *dH, int64_t l
 }  // namespace mgcn
 
 extern "C" int mgcn_gemm_bwd_supported(int32_t F_in, int32_t F_out) {
-  return F_in == kBwF && F_out == kBwF && g_gemm_precision == PREC_BF16X6;
+  return F_in == kBwF && F_out == kBwF && g_opt.gemm_precision == PREC_BF16X6;
 }
 
 extern "C" size_t mgcn_gemm_bwd_workspace_bytes(int64_t M, int32_t F_in, int32_t F_out) {
@@ -2002,7 +1979,7 @@ extern "C" int mgcn_gemm_bwd_dw_cs(int64_t M, const float *X, int64_t ldx, const
                                    void *workspace, size_t workspace_bytes, void *stream) {
   clear_error();
   MGCN_REQUIRE(M >= 0, "mgcn_gemm_bwd_dw_cs: negative size");
-  MGCN_REQUIRE(g_gemm_precision == PREC_BF16X6, "mgcn_gemm_bwd_dw_cs: needs the bf16x6 products");
+  MGCN_REQUIRE(g_opt.gemm_precision == PREC_BF16X6, "mgcn_gemm_bwd_dw_cs: needs the bf16x6 products");
   MGCN_REQUIRE(dW != nullptr && lddw >= kBwF && s_colsum != nullptr,
                "mgcn_gemm_bwd_dw_cs: bad dW / s_colsum");
   hipStream_t s = as_stream(stream);
@@ -2050,7 +2027,7 @@ namespace mgcn {
 // (the workspace's count, K >= 64 rows each) workgroups of >= 256 rows.
 bool tn_staged_plan(int64_t K, int32_t M, int32_t N, const float *A, int64_t lda, const float *B,
                     int64_t ldb, void *workspace, size_t workspace_bytes, TnJob *job) {
-  if (!g_tn_staged || K <= 0 || M != 32 || (N != 32 && N != 64) ||
+  if (!g_opt.gemm_tn_staged || K <= 0 || M != 32 || (N != 32 && N != 64) ||
       reinterpret_cast<uintptr_t>(A) % 16 || reinterpret_cast<uintptr_t>(B) % 16 || lda % 4 ||
       ldb % 4 || workspace == nullptr ||
       workspace_bytes < mgcn_gemm_tn_workspace_bytes(K, M, N))

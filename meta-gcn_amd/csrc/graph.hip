@@ -35,9 +35,6 @@ void set_error(const char *fmt, ...) {
 
 void clear_error() { g_last_error.clear(); }
 
-// warp-specialised hand-off spin bound (mgcn_internal.h; settable in experiment builds)
-uint32_t g_spin_limit = kSpinLimitDefault;
-
 // Device-side failure word (round 6).  One 64-B line of pinned, coherent,
 // portable host memory mapped into every device's address space: a kernel
 // that fails after launch (a warp-specialised kernel whose LDS hand-off spin

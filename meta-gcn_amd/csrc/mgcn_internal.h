@@ -25,8 +25,72 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
 #define MGCN_EXPERIMENT 0
 #endif
 constexpr int kDbgMask = MGCN_EXPERIMENT ? ~0 : 0;  // (a.dbg & kDbgMask): constant 0 in the product
-constexpr uint32_t kSpinLimitDefault = 1u << 25;    // ~1 s of s_sleep(1) polls per hand-off
-extern uint32_t g_spin_limit;                       // kSpinLimitDefault unless an experiment build sets it
+constexpr int kSpinLimitDefault = 1 << 25;          // ~1 s of s_sleep(1) polls per hand-off
+
+// Every mgcn_set_option knob: one field per option, named as the option, at
+// its default.  options.hip holds the table of names and accepted values and
+// is the only writer; include/mgcn.h says what each knob does.
+struct Options {
+  int spmm_vec = 0;  // cap of the floats per lane of the SpMM gathers (0: none)
+  int spmm_unroll = 8;
+  int spmm_unroll_set = 0;    // spmm_unroll given explicitly: every mode takes it
+  int heavy_side_stream = 1;  // heavy-row launch on a side stream (concurrent)
+  int heavy_side_fence = 0;   // 1 = system-scope events on that side stream
+  // LDS per heavy workgroup (two product buffers + the metadata ring).  The
+  // per-batch cost is about one gather round trip, so long rows want big
+  // batches: a giant row's workgroup takes the whole 160 KB of a CU; the other
+  // heavy rows (a few hundred edges) take little, so several share a CU.
+  int heavy_lds_kb = 160;      // giant rows
+  int heavy_mid_lds_kb = 40;   // other heavy rows
+  int heavy_mid_q1 = 1;        // narrow rows: one edge quad in flight
+  int heavy_block = 1024;      // threads per giant-row workgroup
+  int heavy_giant_thr = 512;   // degree above which a heavy row is giant
+  int residual_blocks = 8192;  // residual.hip: workgroups per light-row launch (grid-stride beyond)
+  int residual_fused_mask = 1; // residual.hip: the stack's fused lower-layer mask pass
+  // LDS-staged dW variants (gemm.hip; measured at K = 1M, M = N = 128: 0.321 /
+  // 0.335 / 0.337 ms): 0 = BK 64, one workgroup per CU; 1 = BK 32, two; 2 =
+  // BK 16, three
+  int gemm_tn_variant = 0;
+  int gemm_tn_staged = 1;  // M = 32, N = 32 / 64: gemm_tn_staged_kernel (0: gemm_tn_small_kernel)
+  int gemm_precision = 1;  // gemm.hip: PREC_F32 0 / PREC_BF16X6 1 (gemm_precision_is_x6())
+  int spmm_xw_unroll = 5;  // forward gathers in flight per row (5: config 2 5.06 -> 5.005 ms/step; 6 spills)
+  // the forward's last rounds claimed from a counter (spmm_xw_fwd_kernel DYN;
+  // 0: every chunk static)
+  int xw_dyn_rounds = 8;
+  // 1 = the 128-wide dense forward on spmm_xw_fwd_ws_kernel (default unroll,
+  // a workspace given), 0 = two-phase
+  int xw_fwd_ws = 1;
+  int xw_ws_full = 1;  // the warp-specialised dW + dX adjoint (DWS)
+  int xw_ws_max = 1;   // ... and its max adjoint (DWS + win_mask)
+  int xw_ws_full_unroll = 5;  // DWS gathers in flight per row (5: 0.984-0.991 vs 1.000-1.012 ms at 4)
+  // the sum / mean DWS gather waves' load schedule -- 0 batches, 2 a slot
+  // refilled as it is folded, within a quad and into the next (config 2:
+  // 4.72-4.73 vs 4.82-4.84 ms/step; 1, the refill within a quad alone, gained a
+  // third of that and is removed: DESIGN section 4)
+  int xw_ws_roll = 2;
+  // fused_wide.hip: both rows of a wave's pair gathered together or one after
+  // the other -- bit 0 the forward, bit 1 the adjoint (default 3: both paired)
+  int wide_pair = 3;
+  int wide_ws = 3;    // the 256-wide warp-specialised kernels -- bit 0 the forward, bit 1 the adjoint
+  int wide_mfma = 8;  // MFMA waves of those kernels (4 or 8)
+  // ---- experiment builds only (the product library rejects the names) ----
+  int ws_spin_limit = kSpinLimitDefault;  // the warp-specialised kernels' hand-off bound (abort-path tests)
+  // timing experiments on the 256-wide warp-specialised kernels (results are
+  // WRONG when set): bit 0 the MFMA waves skip their W loads, bit 1 they skip
+  // the products, bit 2 the gather waves skip the gathers; bits 3 / 4:
+  // s_setprio 2 on the gather / MFMA waves (results stay exact)
+  int wide_dbg = 0;
+  // timing experiments on DWS (dW / dX WRONG when set): bit 0 skip the dW
+  // products, bit 2 skip the X loads, bit 3 skip the W^T reads
+  int xw_ws_dbg = 0;
+  // packed-table forms: slots in flight per row (experiment builds sweep them;
+  // config 2's shape, profiles/r06/packed_unroll_sweep.json: forward 1.20 / 1.27
+  // / 1.39 / 1.41 ms at U = 3 / 4 / 5 / 6 -- the extra registers spill more as U
+  // grows --, adjoint 1.07 / 1.05 / 1.08 ms at 2 / 3 / 4)
+  int xw_pk_unroll = 3;
+  int xw_pk_bwd_unroll = 3;
+};
+extern Options g_opt;
 
 // Device-side failure reporting (round 6): the host-mapped error word
 // (graph.hip).  A kernel that cannot finish its work correctly stores a code
@@ -46,6 +110,15 @@ int take_device_error();
 __device__ inline void report_device_error(unsigned *err, unsigned code) {
   if (err != nullptr && (threadIdx.x & 63) == 0)
     __hip_atomic_store(err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// One gathered edge folded into a lane's four features: acc += x * w, product
+// and sum rounded separately (the SpMM's arithmetic, bit for bit)
+__device__ __forceinline__ void fold4(float (&acc)[4], const float4 &x, float w) {
+  acc[0] = __fadd_rn(acc[0], __fmul_rn(x.x, w));
+  acc[1] = __fadd_rn(acc[1], __fmul_rn(x.y, w));
+  acc[2] = __fadd_rn(acc[2], __fmul_rn(x.z, w));
+  acc[3] = __fadd_rn(acc[3], __fmul_rn(x.w, w));
 }
 
 // Check the last launch on this thread; record the HIP error string on failure.
@@ -94,16 +167,17 @@ inline unsigned grid_for(int64_t work_items, int block) {
   return static_cast<unsigned>(g);
 }
 
-// mgcn_set_option("gemm_tn_variant") -> gemm.hip
-int gemm_set_tn_variant(int value);
-int gemm_set_tn_staged(int value);  // mgcn_set_option("gemm_tn_staged")
-int gemm_set_precision(int value);
+// CUs of the current device (256 where the query fails), for grids sized per
+// CU.  Asked on every call: the current device changes between calls.
+inline int device_cus() {
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cus = 256;
+  return cus;
+}
+
 int gemm_precision_is_x6();  // 1 under bf16x6 (the fused kernels need it)
-int xw_set_unroll(int value);  // fused.hip
-int xw_set_dyn_rounds(int value);  // fused.hip: "xw_dyn_rounds"
-int xw_set_ws(const char *name, int value);  // fused.hip: "xw_ws" / "xw_ws_unroll"
-extern int g_fused_mask;       // residual.hip: the stack's fused lower-layer mask pass
-extern int g_rl_cap;           // residual.hip: workgroups per light-row launch (grid-stride beyond)
 // deterministic folds of per-workgroup partials (gemm.hip)
 // deterministic fold of split partials: C[e] (+)= sum_sp partial[sp * MN + e]
 int launch_fold(const float *partial, int64_t splits, int64_t MN, int N, float *C, int64_t ldc,
@@ -207,6 +281,5 @@ int xw_wide_bwd_dx(int64_t n_rows, const int64_t *rowptr_t, const int32_t *col_t
                    const uint32_t *relu_mask, const float *row_div, float *colsum,
                    int accumulate, void *workspace, hipStream_t s,
                    const mgcn_packed_table *pk = nullptr);
-int wide_set_option(const char *name, int value);  // "wide_pair" / "wide_unroll" / "wide_ws"
 
 }  // namespace mgcn

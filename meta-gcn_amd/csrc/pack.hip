@@ -490,7 +490,7 @@ extern "C" int mgcn_pack_rows(int64_t n, int32_t F, const float *X, int64_t ldx,
   unsigned *ticket = static_cast<unsigned *>(workspace);
   uint64_t *status = reinterpret_cast<uint64_t *>(static_cast<char *>(workspace) + 16);
   PK_DISPATCH(pk_group(F), pack_rows_kernel, dim3((unsigned)n_tiles), dim3(64 * kPkWaves), 0, s,
-              n, X, ldx, hdr, vals, total, status, ticket, n_tiles, g_spin_limit, err);
+              n, X, ldx, hdr, vals, total, status, ticket, n_tiles, (uint32_t)g_opt.ws_spin_limit, err);
   return check_launch("pack_rows_kernel");
 }
 

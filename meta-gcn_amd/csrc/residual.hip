@@ -492,14 +492,11 @@ int mask_parts(int64_t n) {
 
 // blocks of one launch: grid-stride beyond (W / Wr^T staged once per block);
 // with the fused mask pass, each block also writes one partial of the sums
-}  // namespace
-int g_rl_cap = 8192;  // mgcn_set_option("residual_blocks"): workgroups per light-row launch
-namespace {
 int64_t rl_blocks(int64_t n_items, bool fused_mask) {
   if (n_items <= 0) return 0;
   const int64_t waves = (n_items + kTileRows - 1) / kTileRows;
   int64_t blocks = (waves + kRWaves - 1) / kRWaves;
-  int64_t cap = g_rl_cap;
+  int64_t cap = g_opt.residual_blocks;
   if (fused_mask && cap > kMaxRlParts) cap = kMaxRlParts;
   return blocks > cap ? cap : blocks;
 }
@@ -595,7 +592,6 @@ extern "C" int mgcn_residual_layer_fwd(int64_t n_rows, int32_t F, const int64_t 
 }
 
 namespace mgcn {
-int g_fused_mask = 1;  // mgcn_set_option("residual_fused_mask")
 namespace {
 // The mask pass of the layer below, fused into this layer's dX store (stack
 // backward): its masks / flags / mean divisor, where dS and dA go, the block
@@ -864,7 +860,7 @@ extern "C" int mgcn_residual_stack_bwd(int64_t n_rows, int32_t F, int32_t n_laye
       lm.partial = fpart + (size_t)c * sc.fpart_half / sizeof(float);
       lm.colsums = sums + (int64_t)(l - 1) * 2 * F;
     }
-    const bool fuse = l > 0 && g_fused_mask;
+    const bool fuse = l > 0 && g_opt.residual_fused_mask;
     // [dW | dWr^T] = X_l^T [dH | dS]: on the staged GEMM's workgroups of the
     // heavy-row transform launch where there is one, else its own launch
     const float *xin = l == 0 ? X0 : Z + (int64_t)(l - 1) * n_rows * F;

@@ -472,11 +472,6 @@ int launch_relu_mask(int64_t n, int F, const float *Y, int64_t ldy, const int32_
   return check_launch("relu_mask_kernel");
 }
 
-int g_force_vec = 0;  // tuning knobs (mgcn_set_option)
-int g_unroll = 8;
-bool g_unroll_set = false;  // spmm_unroll given explicitly: every mode takes it
-int g_heavy_side = 1;  // heavy-row launch on a side stream (concurrent)
-
 template <int VEC, int G, int U, int MODE>
 int launch_one(const SpmmArgs &a, hipStream_t stream) {
   constexpr int RPW = 64 / G;
@@ -493,33 +488,23 @@ template <int VEC, int MODE>
 int launch_g(const SpmmArgs &a, hipStream_t stream) {
   const int lanes = (a.F + VEC - 1) / VEC;
   if (lanes > 32) {
-    if (g_unroll == 16) return launch_one<VEC, 64, 16, MODE>(a, stream);
-    if (g_unroll == 4) return launch_one<VEC, 64, 4, MODE>(a, stream);
+    if (g_opt.spmm_unroll == 16) return launch_one<VEC, 64, 16, MODE>(a, stream);
+    if (g_opt.spmm_unroll == 4) return launch_one<VEC, 64, 4, MODE>(a, stream);
     return launch_one<VEC, 64, 8, MODE>(a, stream);
   }
   if (lanes > 16) {
-    if (g_unroll == 16) return launch_one<VEC, 32, 16, MODE>(a, stream);
+    if (g_opt.spmm_unroll == 16) return launch_one<VEC, 32, 16, MODE>(a, stream);
     // the forward max at U = 8 holds 104 VGPRs (4 waves per SIMD); at U = 6
     // it fits 93 (5 waves, the sum kernel's occupancy, 30 rows in flight per
     // SIMD lane slot against U = 4's 20)
-    if (g_unroll == 6 || (MODE == FWD_MAX && !g_unroll_set)) return launch_one<VEC, 32, 6, MODE>(a, stream);
-    if (g_unroll == 4) return launch_one<VEC, 32, 4, MODE>(a, stream);
+    if (g_opt.spmm_unroll == 6 || (MODE == FWD_MAX && !g_opt.spmm_unroll_set)) return launch_one<VEC, 32, 6, MODE>(a, stream);
+    if (g_opt.spmm_unroll == 4) return launch_one<VEC, 32, 4, MODE>(a, stream);
     return launch_one<VEC, 32, 8, MODE>(a, stream);
   }
   if (lanes > 8) return launch_one<VEC, 16, 8, MODE>(a, stream);
   if (lanes > 4) return launch_one<VEC, 8, 8, MODE>(a, stream);
   return launch_one<VEC, 4, 4, MODE>(a, stream);
 }
-
-// LDS per heavy workgroup (two product buffers + the metadata ring).  The
-// per-batch cost is about one gather round trip, so long rows want big
-// batches: a giant row's workgroup takes the whole 160 KB of a CU; the other
-// heavy rows (a few hundred edges) take little, so several share a CU.
-int g_heavy_lds = 160 * 1024;     // giant rows
-int g_heavy_mid_lds = 40 * 1024;  // other heavy rows
-int g_heavy_mid_q1 = 1;           // narrow rows: one edge quad in flight (heavy_mid_q1)
-int g_heavy_block = 1024;         // threads per giant-row workgroup
-int64_t g_giant_thr = 512;        // degree above which a heavy row is giant
 
 template <int VEC, int MODE, int HB, int Q>
 int launch_heavy_q(const SpmmArgs &a, int64_t n, int FC, int BE, size_t lds, hipStream_t stream) {
@@ -557,7 +542,7 @@ int launch_heavy_hb(SpmmArgs a, const int32_t *rows, int64_t n, int lds_budget,
   // one edge quad in flight per producer (84 VGPRs instead of 172-188, so
   // LDS, not registers, sets the workgroups per CU): 2.77 -> 2.67 ms/step
   if constexpr (HB == 256)
-    if (FC <= 32 && g_heavy_mid_q1) return launch_heavy_q<VEC, MODE, HB, 1>(a, n, FC, BE, lds, stream);
+    if (FC <= 32 && g_opt.heavy_mid_q1) return launch_heavy_q<VEC, MODE, HB, 1>(a, n, FC, BE, lds, stream);
   return launch_heavy_q<VEC, MODE, HB, 0>(a, n, FC, BE, lds, stream);
 }
 
@@ -565,12 +550,12 @@ template <int VEC, int MODE>
 int launch_heavy(const SpmmArgs &a, bool giant, hipStream_t stream) {
   if (!giant)
     return launch_heavy_hb<VEC, MODE, 256>(a, a.order + a.n_giant, a.n_heavy - a.n_giant,
-                                           g_heavy_mid_lds, stream);
-  if (g_heavy_block == 256)
-    return launch_heavy_hb<VEC, MODE, 256>(a, a.order, a.n_giant, g_heavy_lds, stream);
-  if (g_heavy_block == 512)
-    return launch_heavy_hb<VEC, MODE, 512>(a, a.order, a.n_giant, g_heavy_lds, stream);
-  return launch_heavy_hb<VEC, MODE, 1024>(a, a.order, a.n_giant, g_heavy_lds, stream);
+                                           g_opt.heavy_mid_lds_kb * 1024, stream);
+  if (g_opt.heavy_block == 256)
+    return launch_heavy_hb<VEC, MODE, 256>(a, a.order, a.n_giant, g_opt.heavy_lds_kb * 1024, stream);
+  if (g_opt.heavy_block == 512)
+    return launch_heavy_hb<VEC, MODE, 512>(a, a.order, a.n_giant, g_opt.heavy_lds_kb * 1024, stream);
+  return launch_heavy_hb<VEC, MODE, 1024>(a, a.order, a.n_giant, g_opt.heavy_lds_kb * 1024, stream);
 }
 
 template <int MODE>
@@ -588,7 +573,6 @@ struct SideStream {
   hipEvent_t fork = nullptr, join = nullptr;   // device-scope release (same-GPU streams)
   hipEvent_t fork_sys = nullptr, join_sys = nullptr;  // with the system-scope fence
 };
-int g_side_fence = 0;  // mgcn_set_option("heavy_side_fence"): 1 = system-scope events
 
 int side_stream(SideStream **out) {
   static thread_local SideStream per_dev[64];  // per host thread: events never shared
@@ -608,7 +592,7 @@ int side_stream(SideStream **out) {
   }
   static thread_local SideStream view[64];
   view[dev] = s;
-  if (g_side_fence) view[dev].fork = s.fork_sys, view[dev].join = s.join_sys;
+  if (g_opt.heavy_side_fence) view[dev].fork = s.fork_sys, view[dev].join = s.join_sys;
   *out = &view[dev];
   return MGCN_OK;
 }
@@ -628,7 +612,7 @@ int launch_mode(SpmmArgs a, int vec, hipStream_t stream) {
   }
   SideStream *side = nullptr;
   if (a.n_giant > 0) {
-    if (g_heavy_side) {
+    if (g_opt.heavy_side_stream) {
       if (int rc = side_stream(&side)) return rc;
       MGCN_HIP_TRY(hipEventRecord(side->fork, stream));
       MGCN_HIP_TRY(hipStreamWaitEvent(side->stream, side->fork, 0));
@@ -694,7 +678,7 @@ int heavy_rows(int bwd, int64_t n_rows, int32_t F, const int64_t *rowptr, const 
   const int vec = pick_vec(F, X, ldx, Y, ldy);
   if (n_giant > 0) {
     SideStream *side = nullptr;
-    if (g_heavy_side) {
+    if (g_opt.heavy_side_stream) {
       if (int rc = side_stream(&side)) return rc;
       MGCN_HIP_TRY(hipEventRecord(side->fork, stream));
       MGCN_HIP_TRY(hipStreamWaitEvent(side->stream, side->fork, 0));
@@ -734,101 +718,9 @@ extern "C" int mgcn_debug_heavy_prof(unsigned long long *host) {
 }
 #endif
 
-extern "C" int mgcn_set_option(const char *name, int value) {
-  clear_error();
-  MGCN_REQUIRE(name != nullptr, "mgcn_set_option: null name");
-  const std::string n(name);
-  if (n == "spmm_vec") {
-    MGCN_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4, "spmm_vec must be 0,1,2,4");
-    g_force_vec = value;
-    return MGCN_OK;
-  }
-  if (n == "spmm_unroll") {
-    MGCN_REQUIRE(value == 4 || value == 6 || value == 8 || value == 16,
-                 "spmm_unroll must be 4, 6, 8 or 16");
-    g_unroll = value;
-    g_unroll_set = true;
-    return MGCN_OK;
-  }
-  if (n == "heavy_lds_kb") {
-    MGCN_REQUIRE(value >= 16 && value <= 160, "heavy_lds_kb must be in [16, 160]");
-    g_heavy_lds = value * 1024;
-    return MGCN_OK;
-  }
-  if (n == "heavy_block") {
-    MGCN_REQUIRE(value == 256 || value == 512 || value == 1024, "heavy_block must be 256, 512 or 1024");
-    g_heavy_block = value;
-    return MGCN_OK;
-  }
-  if (n == "heavy_mid_q1") {
-    MGCN_REQUIRE(value == 0 || value == 1, "heavy_mid_q1 must be 0 or 1");
-    g_heavy_mid_q1 = value;
-    return MGCN_OK;
-  }
-  if (n == "heavy_mid_lds_kb") {
-    MGCN_REQUIRE(value >= 16 && value <= 160, "heavy_mid_lds_kb must be in [16, 160]");
-    g_heavy_mid_lds = value * 1024;
-    return MGCN_OK;
-  }
-  if (n == "heavy_giant_thr") {
-    MGCN_REQUIRE(value >= 0, "heavy_giant_thr must be >= 0");
-    g_giant_thr = value;
-    return MGCN_OK;
-  }
-  if (n == "gemm_tn_variant") {
-    MGCN_REQUIRE(value >= 0 && value <= 2, "gemm_tn_variant must be 0, 1 or 2");
-    return gemm_set_tn_variant(value);
-  }
-  if (n == "gemm_tn_staged") {
-    MGCN_REQUIRE(value == 0 || value == 1, "gemm_tn_staged must be 0 or 1");
-    return gemm_set_tn_staged(value);
-  }
-  if (n == "gemm_precision") {
-    MGCN_REQUIRE(value == 0 || value == 1, "gemm_precision must be 0 (f32) or 1 (bf16x6)");
-    return gemm_set_precision(value);
-  }
-  if (n == "spmm_xw_unroll") return xw_set_unroll(value);
-  if (n == "xw_dyn_rounds") return xw_set_dyn_rounds(value);
-  if (n == "xw_ws_dbg" || n == "xw_ws_full" || n == "xw_ws_max" || n == "xw_ws_full_unroll" ||
-      n == "xw_ws_roll" || n == "xw_fwd_ws" || n == "xw_pk_unroll" || n == "xw_pk_bwd_unroll")
-    return xw_set_ws(name, value);
-  if (n == "wide_pair" || n == "wide_ws" || n == "wide_dbg" || n == "wide_mfma") return wide_set_option(name, value);
-  if (n == "residual_blocks") {
-    MGCN_REQUIRE(value >= 64 && value <= 65536, "residual_blocks must be in [64, 65536]");
-    g_rl_cap = value;
-    return MGCN_OK;
-  }
-  if (n == "residual_fused_mask") {
-    MGCN_REQUIRE(value == 0 || value == 1, "residual_fused_mask must be 0 or 1");
-    g_fused_mask = value;
-    return MGCN_OK;
-  }
-  if (n == "heavy_side_fence") {
-    MGCN_REQUIRE(value == 0 || value == 1, "heavy_side_fence must be 0 or 1");
-    g_side_fence = value;
-    return MGCN_OK;
-  }
-  if (n == "ws_spin_limit") {  // the warp-specialised kernels' hand-off bound (abort-path tests)
-    if (!MGCN_EXPERIMENT) {
-      set_error("ws_spin_limit: experiment builds only (make exp -> libmgcn_exp.so)");
-      return MGCN_EINVAL;
-    }
-    MGCN_REQUIRE(value >= 1, "ws_spin_limit must be >= 1");
-    g_spin_limit = (uint32_t)value;
-    return MGCN_OK;
-  }
-  if (n == "heavy_side_stream") {
-    MGCN_REQUIRE(value == 0 || value == 1, "heavy_side_stream must be 0 or 1");
-    g_heavy_side = value;
-    return MGCN_OK;
-  }
-  set_error("mgcn_set_option: unknown option '%s'", name);
-  return MGCN_EINVAL;
-}
-
 static int choose_vec(int32_t F, const void *p0, int64_t ld0, const void *p1, int64_t ld1) {
   int v = pick_vec(F, p0, ld0, p1, ld1);
-  if (g_force_vec != 0 && g_force_vec < v) v = g_force_vec;
+  if (g_opt.spmm_vec != 0 && g_opt.spmm_vec < v) v = g_opt.spmm_vec;
   return v;
 }
 
@@ -994,7 +886,7 @@ extern "C" int mgcn_row_schedule(int64_t n_rows, const int64_t *rowptr, int64_t 
   hipStream_t st = as_stream(stream);
   MGCN_HIP_TRY(hipMemsetAsync(count, 0, 2 * sizeof(unsigned long long), st));
   hipLaunchKernelGGL(row_degree_kernel, dim3(grid_for(n_rows, kBlock)), dim3(kBlock), 0, st,
-                     n_rows, rowptr, heavy_thr, g_giant_thr, deg, iota, count);
+                     n_rows, rowptr, heavy_thr, (int64_t)g_opt.heavy_giant_thr, deg, iota, count);
   if (int rc = check_launch("row_degree_kernel")) return rc;
   // stable: equal degrees keep ascending row ids
   MGCN_HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(

@@ -1,5 +1,5 @@
 // bf16x6 product arithmetic and LDS image helpers shared by gemm.hip and
-// fused.hip (internal, device code only).
+// the fused layer kernels (internal, device code only).
 //
 // Every fp32 operand is split exactly-rounded into three bf16 terms
 // x = hi + mid + lo (RNE at each step; x - hi and r - mid are exact,

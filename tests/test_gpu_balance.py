@@ -1,4 +1,4 @@
-"""The dynamic claim of the 128-wide forward's last rounds (fused.hip,
+"""The dynamic claim of the 128-wide forward's last rounds (fused_fwd.hip,
 spmm_xw_fwd_kernel DYN; mgcn_set_option "xw_dyn_rounds", default 8): which
 workgroup runs a chunk of the tail is decided on the device, what it computes
 is not.

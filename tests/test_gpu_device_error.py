@@ -1,7 +1,7 @@
 """Device-side failure reporting of the warp-specialised kernels (round 6,
 ABI 21: mgcn_check_device / MGCN_EDEVICE).
 
-The 128-wide adjoint (fused.hip, spmm_xw_bwd_ws_kernel) and the 256-wide layer
+The 128-wide adjoint (fused_dws.hip, spmm_xw_bwd_ws_kernel) and the 256-wide layer
 kernels (fused_wide.hip, spmm_xw_wide_ws_kernel) hand chunks between their
 gather and MFMA waves through LDS counters with bounded spins.  A spin past
 its bound makes every wave leave, and the kernel's outputs are then

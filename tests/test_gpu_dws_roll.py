@@ -1,4 +1,4 @@
-"""The rolling gather of the warp-specialised F = 128 adjoint (fused.hip,
+"""The rolling gather of the warp-specialised F = 128 adjoint (fused_dws.hip,
 spmm_xw_bwd_ws_kernel, mgcn_set_option "xw_ws_roll"): 0 issues a row quad's
 gathers in batches, 2 (the default) refills a slot as soon as it is folded and
 hands the last slots of a quad to the wave's next quad.  (1, the refill within

@@ -1,4 +1,4 @@
-"""GPU parity of the warp-specialised F = 128 adjoint (fused.hip,
+"""GPU parity of the warp-specialised F = 128 adjoint (fused_dws.hip,
 spmm_xw_bwd_ws_kernel, DWS): mgcn_spmm_xw_bwd's dW + dX form (mgcn_set_option
 "xw_ws_full" 1, the default), its max adjoint and its dY column sums
 (mgcn_spmm_xw_bwd_hcs), against the two-phase kernel and the oracle; the

@@ -1,4 +1,4 @@
-"""The warp-specialised 128-wide fused forward (fused.hip,
+"""The warp-specialised 128-wide fused forward (fused_fwd_ws.hip,
 spmm_xw_fwd_ws_kernel; mgcn_set_option "xw_fwd_ws" 1) against the two-phase
 kernel ("xw_fwd_ws" 0) through mgcn_spmm_xw_fwd itself: the forms differ in
 which wave does what and when a load is issued, never in what is folded or

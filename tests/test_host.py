@@ -46,6 +46,65 @@ def test_abi_version_and_option_errors():
     mgcn.set_option("spmm_unroll", 8)
 
 
+# name: (default, one accepted non-default value or None, one rejected value)
+OPTIONS = {
+    "spmm_vec": (0, 2, 3),
+    "spmm_unroll": (8, 6, 5),
+    "heavy_side_stream": (1, 0, 2),
+    "heavy_side_fence": (0, 1, -1),
+    "heavy_lds_kb": (160, 16, 161),
+    "heavy_block": (1024, 256, 128),
+    "heavy_mid_lds_kb": (40, 160, 15),
+    "heavy_mid_q1": (1, 0, 2),
+    "heavy_giant_thr": (512, 0, -1),
+    "residual_blocks": (8192, 65536, 63),
+    "residual_fused_mask": (1, 0, 2),
+    "gemm_tn_variant": (0, 2, 3),
+    "gemm_tn_staged": (1, 0, 2),
+    "gemm_precision": (1, 0, 2),
+    "spmm_xw_unroll": (5, 8, 7),
+    "xw_dyn_rounds": (8, 64, 65),
+    "xw_fwd_ws": (1, 0, 2),
+    "xw_ws_full": (1, 0, -1),
+    "xw_ws_max": (1, 0, 2),
+    "xw_ws_full_unroll": (5, 6, 7),
+    "xw_ws_roll": (2, 0, 1),
+    "wide_ws": (3, 0, 4),
+    "wide_pair": (3, 1, -1),
+    "wide_mfma": (8, 4, 6),
+    # experiment builds only: the product library rejects the names
+    "ws_spin_limit": (1 << 25, None, 1),
+    "wide_dbg": (0, None, 1),
+    "xw_ws_dbg": (0, None, 1),
+    "xw_pk_unroll": (3, None, 3),
+    "xw_pk_bwd_unroll": (3, None, 3),
+}
+EXPERIMENT_ONLY = {"ws_spin_limit", "wide_dbg", "xw_ws_dbg", "xw_pk_unroll", "xw_pk_bwd_unroll"}
+
+
+def test_every_option_accepts_rejects_and_keeps_its_default():
+    """mgcn_set_option against the table above, which names what mgcn.h documents."""
+    import mgcn
+    lib = mgcn.load()
+    comment = re.search(r"/\* Tuning knobs.*?\*/\s*int mgcn_set_option", open(HEADER).read(), re.S)
+    documented = set(re.findall(r'"(\w+)"\s*:', comment.group(0)))
+    assert set(OPTIONS) == documented | EXPERIMENT_ONLY
+    assert not documented & {"xw_pk_unroll", "xw_pk_bwd_unroll"}
+    for name, (default, accepted, rejected) in OPTIONS.items():
+        key = name.encode()
+        if name in EXPERIMENT_ONLY:
+            assert accepted is None
+            for value in (default, rejected):
+                assert lib.mgcn_set_option(key, value) == 1, name
+                assert b"experiment builds only" in lib.mgcn_last_error(), name
+            continue
+        assert lib.mgcn_set_option(key, rejected) == 1, name
+        assert key in lib.mgcn_last_error(), name
+        assert accepted != default
+        assert lib.mgcn_set_option(key, accepted) == 0, name
+        assert lib.mgcn_set_option(key, default) == 0, name
+
+
 def test_c_abi_rejects_bad_arguments_without_touching_memory():
     """Argument validation happens on the host before any launch."""
     import mgcn
