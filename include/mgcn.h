@@ -1062,6 +1062,92 @@ int mgcn_hatt_gather(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const in
                      const int32_t *col, const float *alpha, const float *Hp, int64_t ldh,
                      float *Y, int64_t ldy, void *stream);
 
+/* ---------------------------- attention and hard attention on bf16 rows */
+
+/*
+ * The _bf16 sibling of every attention / hard-attention entry that reads or
+ * writes a feature row.  Added under ABI 22 without changing any existing
+ * entry (backward-compatible: MGCN_ABI_VERSION stays 22).  mgcn_edge_softmax,
+ * mgcn_hatt_edge_softmax and mgcn_hatt_select touch fp32 scores alone and
+ * serve both row types.
+ *
+ * bf16 (bit patterns as uint16_t; leading dimensions counted in elements):
+ * Hp, Y, dY, dHp.  fp32 as in the entries above: s_src / s_dst, alpha, mask,
+ * noise, dz, ds_src / ds_dst and the attention vector a.
+ *
+ * Contract (that of mgcn_spmm_fwd_bf16): a loaded bf16 element is widened to
+ * fp32 exactly; every value is then formed by the operations of the fp32
+ * entry in the same order; each bf16 output element is rounded once, to
+ * nearest even, at its store.  So every fp32 output (scores, alpha, dz, ds)
+ * has the bits of the fp32 entry called on the upcast rows, and every bf16
+ * output the bits of the fp32 entry's output rounded to bf16.
+ *
+ * Shapes, limits, error behaviour and determinism are those of the fp32
+ * entries: 1 <= H <= 16, C >= 1, H C <= 1024, any leading dimension >= H C
+ * and any element offset (rows need no alignment beyond the 2 bytes of an
+ * element: every row access is a 2-byte load or store).
+ *
+ * att_dir 'out': mgcn_att_bwd_src stores dHp and mgcn_att_dst_fold adds a
+ * term to it, which would round a bf16 row twice.  With dHp_f32 != NULL
+ * ([n_rows, H C] fp32, contiguous, caller-provided) mgcn_att_bwd_src_bf16 /
+ * mgcn_hatt_bwd_src_bf16 park the unrounded row there and do not touch dHp
+ * (which may then be NULL); mgcn_att_dst_fold_bf16 reads it, adds its term in
+ * fp32 and stores the row to dHp, rounded once.  With dHp_f32 == NULL ('in',
+ * and the eval branch of hard attention) the row is rounded and stored to dHp
+ * by mgcn_att_bwd_src_bf16 itself.
+ */
+int mgcn_att_scores_bf16(int64_t n, int32_t H, int32_t C, const uint16_t *Hp, int64_t ldh,
+                         const float *a, float *s_src, float *s_dst, void *stream);
+
+int mgcn_att_fwd_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr,
+                      const int32_t *col, const float *s_row, const float *s_col, int act,
+                      const float *alpha_in, const float *mask, const uint16_t *Hp, int64_t ldh,
+                      uint16_t *Y, int64_t ldy, float *alpha, void *stream);
+
+int mgcn_att_bwd_dst_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                          const int64_t *rowptr, const int32_t *col, const uint16_t *Hp,
+                          int64_t ldh, const uint16_t *dY, int64_t lddy, const float *alpha,
+                          const float *mask, const float *s_row, const float *s_col, int act,
+                          int softmax, float *dz, float *ds_row, void *stream);
+
+int mgcn_att_bwd_src_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                          const int64_t *rowptr_t, const int32_t *col_t, const int32_t *slot_map,
+                          const uint16_t *dY, int64_t lddy, const float *alpha, const float *mask,
+                          float *dz, const float *s_row, const float *s_col, int act, int softmax,
+                          const float *a, const float *ds_dst, float *ds_src, uint16_t *dHp,
+                          int64_t lddh, float *dHp_f32, void *stream);
+
+/* dHp[row,h,:] = round(dHp_f32[row,h,:] + ds_dst[row,h] a[h,C:]) */
+int mgcn_att_dst_fold_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                           const int64_t *rowptr, const float *dz, const float *a, float *ds_dst,
+                           const float *dHp_f32, uint16_t *dHp, int64_t lddh, void *stream);
+
+int mgcn_hatt_fwd_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr,
+                       const int32_t *col, const float *s_row, const float *s_col, int act,
+                       const float *noise, float temperature, const float *alpha_in,
+                       const float *mask, const uint16_t *Hp, int64_t ldh, uint16_t *Y,
+                       int64_t ldy, float *alpha, void *stream);
+
+int mgcn_hatt_bwd_dst_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                           const int64_t *rowptr, const int32_t *col, const uint16_t *Hp,
+                           int64_t ldh, const uint16_t *dY, int64_t lddy, const float *alpha,
+                           const float *mask, const float *s_row, const float *s_col, int act,
+                           int softmax, float temperature, float *dz, float *ds_row,
+                           void *stream);
+
+int mgcn_hatt_bwd_src_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                           const int64_t *rowptr_t, const int32_t *col_t, const int32_t *slot_map,
+                           const uint16_t *dY, int64_t lddy, const float *alpha,
+                           const float *mask, float *dz, const float *s_row, const float *s_col,
+                           int act, int softmax, float temperature, const float *a,
+                           const float *ds_dst, float *ds_src, uint16_t *dHp, int64_t lddh,
+                           float *dHp_f32, void *stream);
+
+int mgcn_hatt_gather_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                          const int64_t *rowptr, const int32_t *col, const float *alpha,
+                          const uint16_t *Hp, int64_t ldh, uint16_t *Y, int64_t ldy,
+                          void *stream);
+
 /* ------------------------------------------------ edge-gated node model */
 
 /*

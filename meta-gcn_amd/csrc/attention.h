@@ -5,6 +5,16 @@
 // the soft structs every `if constexpr (A::kHard)` branch drops out and the
 // kernels are the soft ones, source path for source path.  The work split is
 // described at the top of attention.hip.
+//
+// Feature rows (Hp, Y, dY, dHp) have the element type R of the argument
+// struct: float, or bf16 bit patterns as uint16_t (the mgcn_*_bf16 entries).
+// A bf16 element is widened to fp32 exactly at its load (row_ld), every value
+// is then formed by the fp32 kernel's operations in its order, and a bf16
+// output element is rounded once, to nearest even, at its store (row_st): the
+// fp32 outputs (scores, alpha, dz, ds) have the bits of the fp32 entry on the
+// upcast rows, the bf16 outputs those bits rounded.  With R = float row_ld /
+// row_st are the load / store the fp32 kernels always had.  Scores, alpha,
+// mask, noise, dz, ds and the attention vector are fp32 with either R.
 #pragma once
 
 #include "mgcn_internal.h"
@@ -14,6 +24,26 @@ namespace {
 
 constexpr int kAttWaves = 4;
 constexpr int kAttThreads = 64 * kAttWaves;
+
+// Element i of a row array as fp32, 0 when !on.  fp32: the predicated load
+// the kernels always had.  bf16: the same predicated load of 2 bytes, then
+// the exact widening (bits << 16).  The value of the !on side is a zero the
+// compiler cannot see through (an empty asm on a register): with a literal 0
+// it moves the shift into the predicated block, where the shift waits for its
+// own load, and the loads of a gather batch no longer overlap.
+__device__ inline float row_ld(bool on, const float *rows, int64_t i) {
+  return on ? rows[i] : 0.0f;
+}
+__device__ inline float row_ld(bool on, const uint16_t *rows, int64_t i) {
+  uint32_t zero = 0;
+  asm("" : "+s"(zero));
+  const uint32_t r = on ? (uint32_t)rows[i] : zero;
+  return __uint_as_float(r << 16);
+}
+__device__ inline void row_st(float *p, float v) { *p = v; }
+__device__ inline void row_st(uint16_t *p, float v) {  // v_cvt_pk_bf16_f32: RNE
+  *p = __builtin_bit_cast(uint16_t, static_cast<__bf16>(v));
+}
 
 __device__ inline float att_act(float z, int act) {
   if (act == MGCN_ATT_ACT_LRELU) return z > 0.0f ? z : __fmul_rn(z, 0.2f);
@@ -97,27 +127,33 @@ constexpr int gather_unroll() {
 }
 
 // ----------------------------------------------- softmax + weighted gather
-struct FwdArgs {
+template <class R>
+struct FwdArgsT {
+  using Row = R;
   int64_t n_rows;
   int H, C, act;
   const int64_t *rowptr;
   const int32_t *col;
-  const float *s_row, *s_col, *alpha_in, *mask, *Hp;
+  const float *s_row, *s_col, *alpha_in, *mask;
+  const R *Hp;
   int64_t ldh;
-  float *Y;
+  R *Y;
   int64_t ldy;
   float *alpha;
   static constexpr bool kHard = false;
 };
+using FwdArgs = FwdArgsT<float>;
 
 // Hard attention (graph_hard_attention.py:96-110): Gumbel noise and a
 // temperature inside the logit, l = (act(z) + noise) / T; noise is [nnz, H]
 // in the slot order of the view walked, NULL = zeros.
-struct HardFwdArgs : FwdArgs {
+template <class R>
+struct HardFwdArgsT : FwdArgsT<R> {
   const float *noise;
   float temperature;
   static constexpr bool kHard = true;
 };
+using HardFwdArgs = HardFwdArgsT<float>;
 
 // The logit of (slot, head) idx from its pre-activation z.
 template <bool HARD>
@@ -209,7 +245,7 @@ __global__ __launch_bounds__(kAttThreads) void att_fwd_kernel(A a) {
 #pragma unroll
             for (int i = 0; i < FPL; ++i) {
               const int f = lane + 64 * i;
-              hp[u][i] = (on && f < HC) ? a.Hp[c * a.ldh + f] : 0.0f;
+              hp[u][i] = row_ld(on && f < HC, a.Hp, c * a.ldh + f);
             }
           }
 #pragma unroll
@@ -229,31 +265,36 @@ __global__ __launch_bounds__(kAttThreads) void att_fwd_kernel(A a) {
 #pragma unroll
       for (int i = 0; i < FPL; ++i) {
         const int f = lane + 64 * i;
-        if (f < HC) a.Y[row * a.ldy + f] = acc[i];
+        if (f < HC) row_st(a.Y + row * a.ldy + f, acc[i]);
       }
     }
   }
 }
 
 // ------------------------------------------------- adjoint, by destination
-struct BwdDstArgs {
+template <class R>
+struct BwdDstArgsT {
+  using Row = R;
   int64_t n_rows;
   int H, C, act, softmax;
   const int64_t *rowptr;
   const int32_t *col;
-  const float *Hp;
+  const R *Hp;
   int64_t ldh;
-  const float *dY;
+  const R *dY;
   int64_t lddy;
   const float *alpha, *mask, *s_row, *s_col;
   float *dz, *ds_row;
   static constexpr bool kHard = false;
 };
+using BwdDstArgs = BwdDstArgsT<float>;
 
-struct HardBwdDstArgs : BwdDstArgs {
+template <class R>
+struct HardBwdDstArgsT : BwdDstArgsT<R> {
   float temperature;
   static constexpr bool kHard = true;
 };
+using HardBwdDstArgs = HardBwdDstArgsT<float>;
 
 template <int FPL, class A = BwdDstArgs>
 __global__ __launch_bounds__(kAttThreads) void att_bwd_dst_kernel(A a) {
@@ -273,7 +314,7 @@ __global__ __launch_bounds__(kAttThreads) void att_bwd_dst_kernel(A a) {
 #pragma unroll
     for (int i = 0; i < FPL; ++i) {
       const int f = lane + 64 * i;
-      dy[i] = f < HC ? a.dY[row * a.lddy + f] : 0.0f;
+      dy[i] = row_ld(f < HC, a.dY, row * a.lddy + f);
     }
     const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
     float S = 0.0f;  // lane hh < H: sum_k alpha dalpha of head hh
@@ -286,7 +327,7 @@ __global__ __launch_bounds__(kAttThreads) void att_bwd_dst_kernel(A a) {
 #pragma unroll
         for (int i = 0; i < FPL; ++i) {
           const int f = lane + 64 * i;
-          hp[u][i] = (on && f < HC) ? a.Hp[c * a.ldh + f] : 0.0f;
+          hp[u][i] = row_ld(on && f < HC, a.Hp, c * a.ldh + f);
         }
         const bool mine_on = on && lane < H;
         ml[u] = (mine_on && a.mask != nullptr) ? a.mask[(k0 + u) * H + lane] : 1.0f;
@@ -330,25 +371,41 @@ __global__ __launch_bounds__(kAttThreads) void att_bwd_dst_kernel(A a) {
 }
 
 // ------------------------------------------------------ adjoint, by source
-struct BwdSrcArgs {
+template <class R>
+struct BwdSrcArgsT {
+  using Row = R;
   int64_t n_rows;
   int H, C, act, softmax;
   const int64_t *rowptr;
   const int32_t *col, *slot;
-  const float *dY;
+  const R *dY;
   int64_t lddy;
   const float *alpha, *mask;
   float *dz;
   const float *s_row, *s_col, *a, *ds_dst;
-  float *ds_src, *dHp;
+  float *ds_src;
+  R *dHp;
   int64_t lddh;
   static constexpr bool kHard = false;
+  static constexpr bool kPark = false;
+};
+using BwdSrcArgs = BwdSrcArgsT<float>;
+
+// bf16 rows, att_dir 'out': mgcn_att_dst_fold adds a term to dHp after this
+// kernel, and a bf16 row must be rounded once.  With dHp_f32 given
+// ([n_rows, H C] fp32, compact) the unrounded row is parked there and dHp is
+// left to the fold, which adds its term in fp32 and rounds at its store.
+struct BwdSrcArgsBf16 : BwdSrcArgsT<uint16_t> {
+  float *dHp_f32;
+  static constexpr bool kPark = true;
 };
 
-struct HardBwdSrcArgs : BwdSrcArgs {
+template <class B>
+struct HardBwdSrcArgsT : B {
   float temperature;
   static constexpr bool kHard = true;
 };
+using HardBwdSrcArgs = HardBwdSrcArgsT<BwdSrcArgs>;
 
 template <int FPL, class A = BwdSrcArgs>
 __global__ __launch_bounds__(kAttThreads) void att_bwd_src_kernel(A a) {
@@ -382,7 +439,7 @@ __global__ __launch_bounds__(kAttThreads) void att_bwd_src_kernel(A a) {
         for (int i = 0; i < FPL; ++i) {
           const int f = lane + 64 * i;
           const bool ld = on && f < HC;
-          dy[u][i] = ld ? a.dY[c * a.lddy + f] : 0.0f;
+          dy[u][i] = row_ld(ld, a.dY, c * a.lddy + f);
           w[u][i] = ld ? a.alpha[fs[u] * H + hf[i]] : 0.0f;
           if (a.mask != nullptr) w[u][i] = ld ? __fmul_rn(w[u][i], a.mask[fs[u] * H + hf[i]]) : 0.0f;
         }
@@ -427,7 +484,12 @@ __global__ __launch_bounds__(kAttThreads) void att_bwd_src_kernel(A a) {
         float v = __fadd_rn(acc[i], __fmul_rn(ds, a.a[(int64_t)hh * 2 * a.C + c]));
         if (a.ds_dst != nullptr)
           v = __fadd_rn(v, __fmul_rn(a.ds_dst[row * H + hh], a.a[(int64_t)hh * 2 * a.C + a.C + c]));
-        a.dHp[row * a.lddh + f] = v;
+        bool parked = false;
+        if constexpr (A::kPark) {
+          parked = a.dHp_f32 != nullptr;
+          if (parked) a.dHp_f32[row * HC + f] = v;
+        }
+        if (!parked) row_st(a.dHp + row * a.lddh + f, v);
       }
     }
   }
@@ -453,14 +515,16 @@ unsigned att_grid(int64_t n_rows) {
 }  // namespace mgcn
 
 // the supported range, checked on the host before any launch
-#define ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C)                                              \
-  do {                                                                                        \
-    MGCN_REQUIRE((n_rows) >= 0 && (nnz) >= 0, fn ": negative size");                          \
-    MGCN_REQUIRE((H) >= 1 && (H) <= 16, fn ": need 1 <= H <= 16 (H = %d)", (int)(H));          \
-    MGCN_REQUIRE((C) >= 1 && (int64_t)(H) * (C) <= 1024,                                      \
-                 fn ": need C >= 1 and H C <= 1024 (H = %d, C = %d)", (int)(H), (int)(C));     \
-    MGCN_REQUIRE((int64_t)(nnz) * (H) < ((int64_t)1 << 31), fn ": need nnz H < 2^31");         \
+// (fn: the C entry's name, a const char *: the fp32 and the bf16 entry share
+// one templated body)
+#define ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C)                                               \
+  do {                                                                                         \
+    MGCN_REQUIRE((n_rows) >= 0 && (nnz) >= 0, "%s: negative size", fn);                        \
+    MGCN_REQUIRE((H) >= 1 && (H) <= 16, "%s: need 1 <= H <= 16 (H = %d)", fn, (int)(H));        \
+    MGCN_REQUIRE((C) >= 1 && (int64_t)(H) * (C) <= 1024,                                       \
+                 "%s: need C >= 1 and H C <= 1024 (H = %d, C = %d)", fn, (int)(H), (int)(C));   \
+    MGCN_REQUIRE((int64_t)(nnz) * (H) < ((int64_t)1 << 31), "%s: need nnz H < 2^31", fn);       \
   } while (0)
 
 #define ATT_ACT_OK(fn, act) \
-  MGCN_REQUIRE((act) >= MGCN_ATT_ACT_NONE && (act) <= MGCN_ATT_ACT_RELU, fn ": bad act %d", act)
+  MGCN_REQUIRE((act) >= MGCN_ATT_ACT_NONE && (act) <= MGCN_ATT_ACT_RELU, "%s: bad act %d", fn, act)

@@ -36,6 +36,10 @@
 // The lane-layout helpers, the softmax + gather kernel and the two adjoint
 // kernels live in attention.h, shared with hard_attention.hip; the scores and
 // fold kernels and the soft C entries are here.
+//
+// Every entry that reads or writes a feature row has a _bf16 sibling over
+// bf16 rows (the contract at the top of attention.h); the two share one
+// templated body and one kernel source, instantiated per row type.
 
 #include "attention.h"
 
@@ -43,17 +47,18 @@ namespace mgcn {
 namespace {
 
 // ------------------------------------------------------------------ scores
-struct ScoreArgs {
+template <class R>
+struct ScoreArgsT {
   int64_t n;
   int H, C;
-  const float *Hp;
+  const R *Hp;
   int64_t ldh;
   const float *a;
   float *s_src, *s_dst;
 };
 
-template <int FPL>
-__global__ __launch_bounds__(kAttThreads) void att_scores_kernel(ScoreArgs a) {
+template <int FPL, class R = float>
+__global__ __launch_bounds__(kAttThreads) void att_scores_kernel(ScoreArgsT<R> a) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = blockIdx.x * (int64_t)kAttWaves + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kAttWaves;
@@ -73,7 +78,7 @@ __global__ __launch_bounds__(kAttThreads) void att_scores_kernel(ScoreArgs a) {
 #pragma unroll
     for (int i = 0; i < FPL; ++i) {
       const int f = lane + 64 * i;
-      const float x = f < HC ? a.Hp[row * a.ldh + f] : 0.0f;
+      const float x = row_ld(f < HC, a.Hp, row * a.ldh + f);
       ps[i] = __fmul_rn(x, as[i]);
       pd[i] = __fmul_rn(x, ad[i]);
     }
@@ -87,10 +92,13 @@ __global__ __launch_bounds__(kAttThreads) void att_scores_kernel(ScoreArgs a) {
 }
 
 // ------------------------------- 'out': ds_dst and its term of dHp, by row
-__global__ __launch_bounds__(kAttThreads) void att_dst_fold_kernel(
-    int64_t n_rows, int H, int C, const int64_t *__restrict__ rowptr, const float *__restrict__ dz,
-    const float *__restrict__ av, float *__restrict__ ds_dst, float *__restrict__ dHp,
-    int64_t lddh) {
+// The row written is  prev[row] + ds_dst a[:, C:]:  fp32 rows add to dHp in
+// place (prev = dHp); bf16 rows take the unrounded fp32 row mgcn_att_bwd_src
+// parked (prev [n_rows, H C], compact) and round once at the store.
+template <class R>
+__device__ inline void att_dst_fold_rows(int64_t n_rows, int H, int C, const int64_t *rowptr,
+                                         const float *dz, const float *av, float *ds_dst,
+                                         const float *prev, int64_t ldp, R *dHp, int64_t lddh) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = blockIdx.x * (int64_t)kAttWaves + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kAttWaves;
@@ -110,12 +118,123 @@ __global__ __launch_bounds__(kAttThreads) void att_dst_fold_kernel(
       const int f = f0 + lane;
       const int hh = f < HC ? f / C : 0, c = f - hh * C;
       const float ds = __shfl(tot, hh, 64);
-      if (f < HC) {
-        float *p = dHp + row * lddh + f;
-        *p = __fadd_rn(*p, __fmul_rn(ds, av[(int64_t)hh * 2 * C + C + c]));
-      }
+      if (f < HC)
+        row_st(dHp + row * lddh + f,
+               __fadd_rn(prev[row * ldp + f], __fmul_rn(ds, av[(int64_t)hh * 2 * C + C + c])));
     }
   }
+}
+
+__global__ __launch_bounds__(kAttThreads) void att_dst_fold_kernel(
+    int64_t n_rows, int H, int C, const int64_t *__restrict__ rowptr, const float *__restrict__ dz,
+    const float *__restrict__ av, float *__restrict__ ds_dst, float *dHp, int64_t lddh) {
+  att_dst_fold_rows<float>(n_rows, H, C, rowptr, dz, av, ds_dst, dHp, lddh, dHp, lddh);
+}
+
+__global__ __launch_bounds__(kAttThreads) void att_dst_fold_bf16_kernel(
+    int64_t n_rows, int H, int C, const int64_t *__restrict__ rowptr, const float *__restrict__ dz,
+    const float *__restrict__ av, float *__restrict__ ds_dst, const float *__restrict__ dHp_f32,
+    uint16_t *__restrict__ dHp, int64_t lddh) {
+  att_dst_fold_rows<uint16_t>(n_rows, H, C, rowptr, dz, av, ds_dst, dHp_f32, (int64_t)H * C, dHp,
+                              lddh);
+}
+
+// ------------------------------------------- entry bodies, per row type R
+template <class R>
+int att_scores(const char *fn, int64_t n, int32_t H, int32_t C, const R *Hp, int64_t ldh,
+               const float *a, float *s_src, float *s_dst, void *stream) {
+  clear_error();
+  ATT_REQUIRE_SHAPE(fn, n, 0, H, C);
+  if (n == 0) return MGCN_OK;
+  MGCN_REQUIRE(Hp && a && s_src && s_dst, "%s: null array", fn);
+  MGCN_REQUIRE(ldh >= (int64_t)H * C, "%s: leading dimension too small", fn);
+  ScoreArgsT<R> k{n, H, C, Hp, ldh, a, s_src, s_dst};
+  hipStream_t s = as_stream(stream);
+#define CALL(FPL) \
+  hipLaunchKernelGGL((att_scores_kernel<FPL, R>), dim3(att_grid(n)), dim3(kAttThreads), 0, s, k)
+  ATT_DISPATCH(H * C, CALL);
+#undef CALL
+  return check_launch("att_scores_kernel");
+}
+
+template <class R>
+int att_fwd(const char *fn, int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+            const int64_t *rowptr, const int32_t *col, const float *s_row, const float *s_col,
+            int act, const float *alpha_in, const float *mask, const R *Hp, int64_t ldh, R *Y,
+            int64_t ldy, float *alpha, void *stream) {
+  clear_error();
+  ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C);
+  ATT_ACT_OK(fn, act);
+  if (n_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(rowptr && Hp && Y, "%s: null array", fn);
+  MGCN_REQUIRE(nnz == 0 || col, "%s: null col", fn);
+  MGCN_REQUIRE(alpha_in != nullptr || (s_row && s_col && (alpha || nnz == 0)),
+               "%s: need alpha_in, or s_row / s_col / alpha", fn);
+  MGCN_REQUIRE(ldh >= (int64_t)H * C && ldy >= (int64_t)H * C,
+               "%s: leading dimension too small", fn);
+  FwdArgsT<R> k{n_rows, H, C, act, rowptr, col, s_row, s_col, alpha_in, mask, Hp, ldh, Y, ldy,
+                alpha};
+  hipStream_t s = as_stream(stream);
+#define CALL(FPL)                                                                       \
+  hipLaunchKernelGGL((att_fwd_kernel<FPL, true, FwdArgsT<R>>), dim3(att_grid(n_rows)), \
+                     dim3(kAttThreads), 0, s, k)
+  ATT_DISPATCH(H * C, CALL);
+#undef CALL
+  return check_launch("att_fwd_kernel");
+}
+
+template <class R>
+int att_bwd_dst(const char *fn, int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                const int64_t *rowptr, const int32_t *col, const R *Hp, int64_t ldh, const R *dY,
+                int64_t lddy, const float *alpha, const float *mask, const float *s_row,
+                const float *s_col, int act, int softmax, float *dz, float *ds_row,
+                void *stream) {
+  clear_error();
+  ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C);
+  ATT_ACT_OK(fn, act);
+  if (n_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(rowptr && Hp && dY, "%s: null array", fn);
+  MGCN_REQUIRE(nnz == 0 || (col && dz), "%s: null col / dz", fn);
+  MGCN_REQUIRE(!softmax || (ds_row && s_row && s_col && (alpha || nnz == 0)),
+               "%s: the softmax adjoint needs alpha, s_row, s_col, ds_row", fn);
+  MGCN_REQUIRE(ldh >= (int64_t)H * C && lddy >= (int64_t)H * C,
+               "%s: leading dimension too small", fn);
+  BwdDstArgsT<R> k{n_rows, H, C, act, softmax ? 1 : 0, rowptr, col, Hp, ldh, dY, lddy,
+                   alpha, mask, s_row, s_col, dz, ds_row};
+  hipStream_t s = as_stream(stream);
+#define CALL(FPL)                                                                        \
+  hipLaunchKernelGGL((att_bwd_dst_kernel<FPL, BwdDstArgsT<R>>), dim3(att_grid(n_rows)), \
+                     dim3(kAttThreads), 0, s, k)
+  ATT_DISPATCH(H * C, CALL);
+#undef CALL
+  return check_launch("att_bwd_dst_kernel");
+}
+
+// A: BwdSrcArgs or BwdSrcArgsBf16, filled by the caller
+template <class A>
+int att_bwd_src(const char *fn, const A &k, int64_t nnz, void *stream) {
+  clear_error();
+  const int H = k.H, C = k.C;
+  ATT_REQUIRE_SHAPE(fn, k.n_rows, nnz, H, C);
+  ATT_ACT_OK(fn, k.act);
+  if (k.n_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(k.rowptr && k.dY && k.a && k.ds_src, "%s: null array", fn);
+  MGCN_REQUIRE(nnz == 0 || (k.col && k.slot && k.alpha && k.dz),
+               "%s: null col / slot_map / alpha / dz", fn);
+  MGCN_REQUIRE(!k.softmax || (k.s_row && k.s_col), "%s: the softmax adjoint needs s_row, s_col",
+               fn);
+  bool parked = false;
+  if constexpr (A::kPark) parked = k.dHp_f32 != nullptr;
+  MGCN_REQUIRE(parked || k.dHp, "%s: null dHp", fn);
+  MGCN_REQUIRE(k.lddy >= (int64_t)H * C && (parked || k.lddh >= (int64_t)H * C),
+               "%s: leading dimension too small", fn);
+  hipStream_t s = as_stream(stream);
+#define CALL(FPL)                                                                         \
+  hipLaunchKernelGGL((att_bwd_src_kernel<FPL, A>), dim3(att_grid(k.n_rows)), dim3(kAttThreads), \
+                     0, s, k)
+  ATT_DISPATCH(H * C, CALL);
+#undef CALL
+  return check_launch("att_bwd_src_kernel");
 }
 
 }  // namespace
@@ -125,18 +244,13 @@ using namespace mgcn;
 
 extern "C" int mgcn_att_scores(int64_t n, int32_t H, int32_t C, const float *Hp, int64_t ldh,
                                const float *a, float *s_src, float *s_dst, void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE("mgcn_att_scores", n, 0, H, C);
-  if (n == 0) return MGCN_OK;
-  MGCN_REQUIRE(Hp && a && s_src && s_dst, "mgcn_att_scores: null array");
-  MGCN_REQUIRE(ldh >= (int64_t)H * C, "mgcn_att_scores: leading dimension too small");
-  ScoreArgs k{n, H, C, Hp, ldh, a, s_src, s_dst};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL) \
-  hipLaunchKernelGGL((att_scores_kernel<FPL>), dim3(att_grid(n)), dim3(kAttThreads), 0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_scores_kernel");
+  return att_scores<float>("mgcn_att_scores", n, H, C, Hp, ldh, a, s_src, s_dst, stream);
+}
+
+extern "C" int mgcn_att_scores_bf16(int64_t n, int32_t H, int32_t C, const uint16_t *Hp,
+                                    int64_t ldh, const float *a, float *s_src, float *s_dst,
+                                    void *stream) {
+  return att_scores<uint16_t>("mgcn_att_scores_bf16", n, H, C, Hp, ldh, a, s_src, s_dst, stream);
 }
 
 extern "C" int mgcn_att_fwd(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -144,24 +258,17 @@ extern "C" int mgcn_att_fwd(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
                             const float *s_col, int act, const float *alpha_in,
                             const float *mask, const float *Hp, int64_t ldh, float *Y,
                             int64_t ldy, float *alpha, void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE("mgcn_att_fwd", n_rows, nnz, H, C);
-  ATT_ACT_OK("mgcn_att_fwd", act);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hp && Y, "mgcn_att_fwd: null array");
-  MGCN_REQUIRE(nnz == 0 || col, "mgcn_att_fwd: null col");
-  MGCN_REQUIRE(alpha_in != nullptr || (s_row && s_col && (alpha || nnz == 0)),
-               "mgcn_att_fwd: need alpha_in, or s_row / s_col / alpha");
-  MGCN_REQUIRE(ldh >= (int64_t)H * C && ldy >= (int64_t)H * C,
-               "mgcn_att_fwd: leading dimension too small");
-  FwdArgs k{n_rows, H, C, act, rowptr, col, s_row, s_col, alpha_in, mask, Hp, ldh, Y, ldy, alpha};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                          \
-  hipLaunchKernelGGL((att_fwd_kernel<FPL, true>), dim3(att_grid(n_rows)), dim3(kAttThreads), \
-                     0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_fwd_kernel");
+  return att_fwd<float>("mgcn_att_fwd", n_rows, nnz, H, C, rowptr, col, s_row, s_col, act,
+                        alpha_in, mask, Hp, ldh, Y, ldy, alpha, stream);
+}
+
+extern "C" int mgcn_att_fwd_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                                 const int64_t *rowptr, const int32_t *col, const float *s_row,
+                                 const float *s_col, int act, const float *alpha_in,
+                                 const float *mask, const uint16_t *Hp, int64_t ldh, uint16_t *Y,
+                                 int64_t ldy, float *alpha, void *stream) {
+  return att_fwd<uint16_t>("mgcn_att_fwd_bf16", n_rows, nnz, H, C, rowptr, col, s_row, s_col, act,
+                           alpha_in, mask, Hp, ldh, Y, ldy, alpha, stream);
 }
 
 extern "C" int mgcn_edge_softmax(int64_t n_rows, int64_t nnz, int32_t H, const int64_t *rowptr,
@@ -184,25 +291,19 @@ extern "C" int mgcn_att_bwd_dst(int64_t n_rows, int64_t nnz, int32_t H, int32_t 
                                 int64_t ldh, const float *dY, int64_t lddy, const float *alpha,
                                 const float *mask, const float *s_row, const float *s_col,
                                 int act, int softmax, float *dz, float *ds_row, void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE("mgcn_att_bwd_dst", n_rows, nnz, H, C);
-  ATT_ACT_OK("mgcn_att_bwd_dst", act);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hp && dY, "mgcn_att_bwd_dst: null array");
-  MGCN_REQUIRE(nnz == 0 || (col && dz), "mgcn_att_bwd_dst: null col / dz");
-  MGCN_REQUIRE(!softmax || (ds_row && s_row && s_col && (alpha || nnz == 0)),
-               "mgcn_att_bwd_dst: the softmax adjoint needs alpha, s_row, s_col, ds_row");
-  MGCN_REQUIRE(ldh >= (int64_t)H * C && lddy >= (int64_t)H * C,
-               "mgcn_att_bwd_dst: leading dimension too small");
-  BwdDstArgs k{n_rows, H, C, act, softmax ? 1 : 0, rowptr, col, Hp, ldh, dY, lddy,
-               alpha, mask, s_row, s_col, dz, ds_row};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                            \
-  hipLaunchKernelGGL((att_bwd_dst_kernel<FPL>), dim3(att_grid(n_rows)), dim3(kAttThreads), 0, \
-                     s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_bwd_dst_kernel");
+  return att_bwd_dst<float>("mgcn_att_bwd_dst", n_rows, nnz, H, C, rowptr, col, Hp, ldh, dY, lddy,
+                            alpha, mask, s_row, s_col, act, softmax, dz, ds_row, stream);
+}
+
+extern "C" int mgcn_att_bwd_dst_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                                     const int64_t *rowptr, const int32_t *col,
+                                     const uint16_t *Hp, int64_t ldh, const uint16_t *dY,
+                                     int64_t lddy, const float *alpha, const float *mask,
+                                     const float *s_row, const float *s_col, int act, int softmax,
+                                     float *dz, float *ds_row, void *stream) {
+  return att_bwd_dst<uint16_t>("mgcn_att_bwd_dst_bf16", n_rows, nnz, H, C, rowptr, col, Hp, ldh,
+                               dY, lddy, alpha, mask, s_row, s_col, act, softmax, dz, ds_row,
+                               stream);
 }
 
 extern "C" int mgcn_att_bwd_src(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -212,26 +313,22 @@ extern "C" int mgcn_att_bwd_src(int64_t n_rows, int64_t nnz, int32_t H, int32_t 
                                 const float *s_row, const float *s_col, int act, int softmax,
                                 const float *a, const float *ds_dst, float *ds_src, float *dHp,
                                 int64_t lddh, void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE("mgcn_att_bwd_src", n_rows, nnz, H, C);
-  ATT_ACT_OK("mgcn_att_bwd_src", act);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr_t && dY && a && ds_src && dHp, "mgcn_att_bwd_src: null array");
-  MGCN_REQUIRE(nnz == 0 || (col_t && slot_map && alpha && dz),
-               "mgcn_att_bwd_src: null col / slot_map / alpha / dz");
-  MGCN_REQUIRE(!softmax || (s_row && s_col),
-               "mgcn_att_bwd_src: the softmax adjoint needs s_row, s_col");
-  MGCN_REQUIRE(lddy >= (int64_t)H * C && lddh >= (int64_t)H * C,
-               "mgcn_att_bwd_src: leading dimension too small");
   BwdSrcArgs k{n_rows, H, C, act, softmax ? 1 : 0, rowptr_t, col_t, slot_map, dY, lddy,
                alpha, mask, dz, s_row, s_col, a, ds_dst, ds_src, dHp, lddh};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                            \
-  hipLaunchKernelGGL((att_bwd_src_kernel<FPL>), dim3(att_grid(n_rows)), dim3(kAttThreads), 0, \
-                     s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_bwd_src_kernel");
+  return att_bwd_src("mgcn_att_bwd_src", k, nnz, stream);
+}
+
+extern "C" int mgcn_att_bwd_src_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                                     const int64_t *rowptr_t, const int32_t *col_t,
+                                     const int32_t *slot_map, const uint16_t *dY, int64_t lddy,
+                                     const float *alpha, const float *mask, float *dz,
+                                     const float *s_row, const float *s_col, int act, int softmax,
+                                     const float *a, const float *ds_dst, float *ds_src,
+                                     uint16_t *dHp, int64_t lddh, float *dHp_f32, void *stream) {
+  BwdSrcArgsBf16 k{{n_rows, H, C, act, softmax ? 1 : 0, rowptr_t, col_t, slot_map, dY, lddy,
+                    alpha, mask, dz, s_row, s_col, a, ds_dst, ds_src, dHp, lddh},
+                   dHp_f32};
+  return att_bwd_src("mgcn_att_bwd_src_bf16", k, nnz, stream);
 }
 
 extern "C" int mgcn_att_dst_fold(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -246,4 +343,20 @@ extern "C" int mgcn_att_dst_fold(int64_t n_rows, int64_t nnz, int32_t H, int32_t
   hipLaunchKernelGGL(att_dst_fold_kernel, dim3(att_grid(n_rows)), dim3(kAttThreads), 0,
                      as_stream(stream), n_rows, (int)H, (int)C, rowptr, dz, a, ds_dst, dHp, lddh);
   return check_launch("att_dst_fold_kernel");
+}
+
+extern "C" int mgcn_att_dst_fold_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                                      const int64_t *rowptr, const float *dz, const float *a,
+                                      float *ds_dst, const float *dHp_f32, uint16_t *dHp,
+                                      int64_t lddh, void *stream) {
+  clear_error();
+  ATT_REQUIRE_SHAPE("mgcn_att_dst_fold_bf16", n_rows, nnz, H, C);
+  if (n_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(rowptr && a && ds_dst && dHp_f32 && dHp, "mgcn_att_dst_fold_bf16: null array");
+  MGCN_REQUIRE(nnz == 0 || dz, "mgcn_att_dst_fold_bf16: null dz");
+  MGCN_REQUIRE(lddh >= (int64_t)H * C, "mgcn_att_dst_fold_bf16: leading dimension too small");
+  hipLaunchKernelGGL(att_dst_fold_bf16_kernel, dim3(att_grid(n_rows)), dim3(kAttThreads), 0,
+                     as_stream(stream), n_rows, (int)H, (int)C, rowptr, dz, a, ds_dst, dHp_f32,
+                     dHp, lddh);
+  return check_launch("att_dst_fold_bf16_kernel");
 }

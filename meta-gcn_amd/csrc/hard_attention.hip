@@ -12,6 +12,8 @@
 // alpha that is at most H rows per node instead of the whole neighbourhood.
 // Same work split as attention.hip: 4 waves per workgroup, one wave per CSR
 // row, grid-stride over rows, no LDS, no atomics, every sum in a fixed order.
+// The entries that touch a feature row have _bf16 siblings (the row type R of
+// attention.h); select and the edge softmax see fp32 scores alone.
 
 #include "attention.h"
 
@@ -80,14 +82,16 @@ __global__ __launch_bounds__(kAttThreads) void hatt_select_kernel(
   }
 }
 
-struct GatherArgs {
+template <class R>
+struct GatherArgsT {
   int64_t n_rows;
   int H, C;
   const int64_t *rowptr;
   const int32_t *col;
-  const float *alpha, *Hp;
+  const float *alpha;
+  const R *Hp;
   int64_t ldh;
-  float *Y;
+  R *Y;
   int64_t ldy;
 };
 
@@ -97,8 +101,8 @@ struct GatherArgs {
 // slots that own one, in slot order, U at a time.  A skipped term would add
 // +-0 to an accumulator that starts at +0 and so can never be -0: the bits
 // are those of the dense walk.
-template <int FPL>
-__global__ __launch_bounds__(kAttThreads) void hatt_gather_kernel(GatherArgs a) {
+template <int FPL, class R = float>
+__global__ __launch_bounds__(kAttThreads) void hatt_gather_kernel(GatherArgsT<R> a) {
   constexpr int U = gather_unroll<FPL>();
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = blockIdx.x * (int64_t)kAttWaves + (threadIdx.x >> 6);
@@ -134,7 +138,7 @@ __global__ __launch_bounds__(kAttThreads) void hatt_gather_kernel(GatherArgs a) 
 #pragma unroll
           for (int i = 0; i < FPL; ++i) {
             const int f = lane + 64 * i;
-            hp[u][i] = (on && f < HC) ? a.Hp[c * a.ldh + f] : 0.0f;
+            hp[u][i] = row_ld(on && f < HC, a.Hp, c * a.ldh + f);
           }
         }
 #pragma unroll
@@ -152,9 +156,120 @@ __global__ __launch_bounds__(kAttThreads) void hatt_gather_kernel(GatherArgs a) 
 #pragma unroll
     for (int i = 0; i < FPL; ++i) {
       const int f = lane + 64 * i;
-      if (f < HC) a.Y[row * a.ldy + f] = acc[i];
+      if (f < HC) row_st(a.Y + row * a.ldy + f, acc[i]);
     }
   }
+}
+
+#define HATT_TEMPERATURE_OK(fn, T) \
+  MGCN_REQUIRE((T) > 0.0f, "%s: need temperature > 0 (got %g)", fn, (double)(T))
+
+// ------------------------------------------- entry bodies, per row type R
+template <class R>
+int hatt_fwd(const char *fn, int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+             const int64_t *rowptr, const int32_t *col, const float *s_row, const float *s_col,
+             int act, const float *noise, float temperature, const float *alpha_in,
+             const float *mask, const R *Hp, int64_t ldh, R *Y, int64_t ldy, float *alpha,
+             void *stream) {
+  clear_error();
+  ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C);
+  ATT_ACT_OK(fn, act);
+  HATT_TEMPERATURE_OK(fn, temperature);
+  if (n_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(rowptr && Hp && Y, "%s: null array", fn);
+  MGCN_REQUIRE(nnz == 0 || col, "%s: null col", fn);
+  MGCN_REQUIRE(alpha_in != nullptr || (s_row && s_col && (alpha || nnz == 0)),
+               "%s: need alpha_in, or s_row / s_col / alpha", fn);
+  MGCN_REQUIRE(ldh >= (int64_t)H * C && ldy >= (int64_t)H * C,
+               "%s: leading dimension too small", fn);
+  HardFwdArgsT<R> k{{n_rows, H, C, act, rowptr, col, s_row, s_col, alpha_in, mask, Hp, ldh, Y,
+                     ldy, alpha},
+                    noise, temperature};
+  hipStream_t s = as_stream(stream);
+#define CALL(FPL)                                                                           \
+  hipLaunchKernelGGL((att_fwd_kernel<FPL, true, HardFwdArgsT<R>>), dim3(att_grid(n_rows)), \
+                     dim3(kAttThreads), 0, s, k)
+  ATT_DISPATCH(H * C, CALL);
+#undef CALL
+  return check_launch("att_fwd_kernel (hard)");
+}
+
+template <class R>
+int hatt_bwd_dst(const char *fn, int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                 const int64_t *rowptr, const int32_t *col, const R *Hp, int64_t ldh, const R *dY,
+                 int64_t lddy, const float *alpha, const float *mask, const float *s_row,
+                 const float *s_col, int act, int softmax, float temperature, float *dz,
+                 float *ds_row, void *stream) {
+  clear_error();
+  ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C);
+  ATT_ACT_OK(fn, act);
+  HATT_TEMPERATURE_OK(fn, temperature);
+  if (n_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(rowptr && Hp && dY, "%s: null array", fn);
+  MGCN_REQUIRE(nnz == 0 || (col && dz), "%s: null col / dz", fn);
+  MGCN_REQUIRE(!softmax || (ds_row && s_row && s_col && (alpha || nnz == 0)),
+               "%s: the softmax adjoint needs alpha, s_row, s_col, ds_row", fn);
+  MGCN_REQUIRE(ldh >= (int64_t)H * C && lddy >= (int64_t)H * C,
+               "%s: leading dimension too small", fn);
+  HardBwdDstArgsT<R> k{{n_rows, H, C, act, softmax ? 1 : 0, rowptr, col, Hp, ldh, dY, lddy, alpha,
+                        mask, s_row, s_col, dz, ds_row},
+                       temperature};
+  hipStream_t s = as_stream(stream);
+#define CALL(FPL)                                                                            \
+  hipLaunchKernelGGL((att_bwd_dst_kernel<FPL, HardBwdDstArgsT<R>>), dim3(att_grid(n_rows)), \
+                     dim3(kAttThreads), 0, s, k)
+  ATT_DISPATCH(H * C, CALL);
+#undef CALL
+  return check_launch("att_bwd_dst_kernel (hard)");
+}
+
+// A: HardBwdSrcArgsT<BwdSrcArgs> or HardBwdSrcArgsT<BwdSrcArgsBf16>, filled by the caller
+template <class A>
+int hatt_bwd_src(const char *fn, const A &k, int64_t nnz, void *stream) {
+  clear_error();
+  const int H = k.H, C = k.C;
+  ATT_REQUIRE_SHAPE(fn, k.n_rows, nnz, H, C);
+  ATT_ACT_OK(fn, k.act);
+  HATT_TEMPERATURE_OK(fn, k.temperature);
+  if (k.n_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(k.rowptr && k.dY && k.a && k.ds_src, "%s: null array", fn);
+  MGCN_REQUIRE(nnz == 0 || (k.col && k.slot && k.alpha && k.dz),
+               "%s: null col / slot_map / alpha / dz", fn);
+  MGCN_REQUIRE(!k.softmax || (k.s_row && k.s_col), "%s: the softmax adjoint needs s_row, s_col",
+               fn);
+  bool parked = false;
+  if constexpr (A::kPark) parked = k.dHp_f32 != nullptr;
+  MGCN_REQUIRE(parked || k.dHp, "%s: null dHp", fn);
+  MGCN_REQUIRE(k.lddy >= (int64_t)H * C && (parked || k.lddh >= (int64_t)H * C),
+               "%s: leading dimension too small", fn);
+  hipStream_t s = as_stream(stream);
+#define CALL(FPL)                                                                         \
+  hipLaunchKernelGGL((att_bwd_src_kernel<FPL, A>), dim3(att_grid(k.n_rows)), dim3(kAttThreads), \
+                     0, s, k)
+  ATT_DISPATCH(H * C, CALL);
+#undef CALL
+  return check_launch("att_bwd_src_kernel (hard)");
+}
+
+template <class R>
+int hatt_gather(const char *fn, int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                const int64_t *rowptr, const int32_t *col, const float *alpha, const R *Hp,
+                int64_t ldh, R *Y, int64_t ldy, void *stream) {
+  clear_error();
+  ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C);
+  if (n_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(rowptr && Hp && Y, "%s: null array", fn);
+  MGCN_REQUIRE(nnz == 0 || (col && alpha), "%s: null col / alpha", fn);
+  MGCN_REQUIRE(ldh >= (int64_t)H * C && ldy >= (int64_t)H * C,
+               "%s: leading dimension too small", fn);
+  GatherArgsT<R> k{n_rows, H, C, rowptr, col, alpha, Hp, ldh, Y, ldy};
+  hipStream_t s = as_stream(stream);
+#define CALL(FPL)                                                                              \
+  hipLaunchKernelGGL((hatt_gather_kernel<FPL, R>), dim3(att_grid(n_rows)), dim3(kAttThreads), 0, \
+                     s, k)
+  ATT_DISPATCH(H * C, CALL);
+#undef CALL
+  return check_launch("hatt_gather_kernel");
 }
 
 }  // namespace
@@ -162,35 +277,24 @@ __global__ __launch_bounds__(kAttThreads) void hatt_gather_kernel(GatherArgs a) 
 
 using namespace mgcn;
 
-#define HATT_TEMPERATURE_OK(fn, T) \
-  MGCN_REQUIRE((T) > 0.0f, fn ": need temperature > 0 (got %g)", (double)(T))
-
 extern "C" int mgcn_hatt_fwd(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
                              const int64_t *rowptr, const int32_t *col, const float *s_row,
                              const float *s_col, int act, const float *noise, float temperature,
                              const float *alpha_in, const float *mask, const float *Hp,
                              int64_t ldh, float *Y, int64_t ldy, float *alpha, void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE("mgcn_hatt_fwd", n_rows, nnz, H, C);
-  ATT_ACT_OK("mgcn_hatt_fwd", act);
-  HATT_TEMPERATURE_OK("mgcn_hatt_fwd", temperature);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hp && Y, "mgcn_hatt_fwd: null array");
-  MGCN_REQUIRE(nnz == 0 || col, "mgcn_hatt_fwd: null col");
-  MGCN_REQUIRE(alpha_in != nullptr || (s_row && s_col && (alpha || nnz == 0)),
-               "mgcn_hatt_fwd: need alpha_in, or s_row / s_col / alpha");
-  MGCN_REQUIRE(ldh >= (int64_t)H * C && ldy >= (int64_t)H * C,
-               "mgcn_hatt_fwd: leading dimension too small");
-  HardFwdArgs k{{n_rows, H, C, act, rowptr, col, s_row, s_col, alpha_in, mask, Hp, ldh, Y, ldy,
-                 alpha},
-                noise, temperature};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                \
-  hipLaunchKernelGGL((att_fwd_kernel<FPL, true, HardFwdArgs>), dim3(att_grid(n_rows)), \
-                     dim3(kAttThreads), 0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_fwd_kernel (hard)");
+  return hatt_fwd<float>("mgcn_hatt_fwd", n_rows, nnz, H, C, rowptr, col, s_row, s_col, act,
+                         noise, temperature, alpha_in, mask, Hp, ldh, Y, ldy, alpha, stream);
+}
+
+extern "C" int mgcn_hatt_fwd_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                                  const int64_t *rowptr, const int32_t *col, const float *s_row,
+                                  const float *s_col, int act, const float *noise,
+                                  float temperature, const float *alpha_in, const float *mask,
+                                  const uint16_t *Hp, int64_t ldh, uint16_t *Y, int64_t ldy,
+                                  float *alpha, void *stream) {
+  return hatt_fwd<uint16_t>("mgcn_hatt_fwd_bf16", n_rows, nnz, H, C, rowptr, col, s_row, s_col,
+                            act, noise, temperature, alpha_in, mask, Hp, ldh, Y, ldy, alpha,
+                            stream);
 }
 
 extern "C" int mgcn_hatt_edge_softmax(int64_t n_rows, int64_t nnz, int32_t H,
@@ -218,27 +322,21 @@ extern "C" int mgcn_hatt_bwd_dst(int64_t n_rows, int64_t nnz, int32_t H, int32_t
                                  const float *mask, const float *s_row, const float *s_col,
                                  int act, int softmax, float temperature, float *dz,
                                  float *ds_row, void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE("mgcn_hatt_bwd_dst", n_rows, nnz, H, C);
-  ATT_ACT_OK("mgcn_hatt_bwd_dst", act);
-  HATT_TEMPERATURE_OK("mgcn_hatt_bwd_dst", temperature);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hp && dY, "mgcn_hatt_bwd_dst: null array");
-  MGCN_REQUIRE(nnz == 0 || (col && dz), "mgcn_hatt_bwd_dst: null col / dz");
-  MGCN_REQUIRE(!softmax || (ds_row && s_row && s_col && (alpha || nnz == 0)),
-               "mgcn_hatt_bwd_dst: the softmax adjoint needs alpha, s_row, s_col, ds_row");
-  MGCN_REQUIRE(ldh >= (int64_t)H * C && lddy >= (int64_t)H * C,
-               "mgcn_hatt_bwd_dst: leading dimension too small");
-  HardBwdDstArgs k{{n_rows, H, C, act, softmax ? 1 : 0, rowptr, col, Hp, ldh, dY, lddy, alpha,
-                    mask, s_row, s_col, dz, ds_row},
-                   temperature};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                    \
-  hipLaunchKernelGGL((att_bwd_dst_kernel<FPL, HardBwdDstArgs>), dim3(att_grid(n_rows)), \
-                     dim3(kAttThreads), 0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_bwd_dst_kernel (hard)");
+  return hatt_bwd_dst<float>("mgcn_hatt_bwd_dst", n_rows, nnz, H, C, rowptr, col, Hp, ldh, dY,
+                             lddy, alpha, mask, s_row, s_col, act, softmax, temperature, dz,
+                             ds_row, stream);
+}
+
+extern "C" int mgcn_hatt_bwd_dst_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                                      const int64_t *rowptr, const int32_t *col,
+                                      const uint16_t *Hp, int64_t ldh, const uint16_t *dY,
+                                      int64_t lddy, const float *alpha, const float *mask,
+                                      const float *s_row, const float *s_col, int act,
+                                      int softmax, float temperature, float *dz, float *ds_row,
+                                      void *stream) {
+  return hatt_bwd_dst<uint16_t>("mgcn_hatt_bwd_dst_bf16", n_rows, nnz, H, C, rowptr, col, Hp, ldh,
+                                dY, lddy, alpha, mask, s_row, s_col, act, softmax, temperature,
+                                dz, ds_row, stream);
 }
 
 extern "C" int mgcn_hatt_bwd_src(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -248,28 +346,26 @@ extern "C" int mgcn_hatt_bwd_src(int64_t n_rows, int64_t nnz, int32_t H, int32_t
                                  const float *s_row, const float *s_col, int act, int softmax,
                                  float temperature, const float *a, const float *ds_dst,
                                  float *ds_src, float *dHp, int64_t lddh, void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE("mgcn_hatt_bwd_src", n_rows, nnz, H, C);
-  ATT_ACT_OK("mgcn_hatt_bwd_src", act);
-  HATT_TEMPERATURE_OK("mgcn_hatt_bwd_src", temperature);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr_t && dY && a && ds_src && dHp, "mgcn_hatt_bwd_src: null array");
-  MGCN_REQUIRE(nnz == 0 || (col_t && slot_map && alpha && dz),
-               "mgcn_hatt_bwd_src: null col / slot_map / alpha / dz");
-  MGCN_REQUIRE(!softmax || (s_row && s_col),
-               "mgcn_hatt_bwd_src: the softmax adjoint needs s_row, s_col");
-  MGCN_REQUIRE(lddy >= (int64_t)H * C && lddh >= (int64_t)H * C,
-               "mgcn_hatt_bwd_src: leading dimension too small");
   HardBwdSrcArgs k{{n_rows, H, C, act, softmax ? 1 : 0, rowptr_t, col_t, slot_map, dY, lddy,
                     alpha, mask, dz, s_row, s_col, a, ds_dst, ds_src, dHp, lddh},
                    temperature};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                    \
-  hipLaunchKernelGGL((att_bwd_src_kernel<FPL, HardBwdSrcArgs>), dim3(att_grid(n_rows)), \
-                     dim3(kAttThreads), 0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_bwd_src_kernel (hard)");
+  return hatt_bwd_src("mgcn_hatt_bwd_src", k, nnz, stream);
+}
+
+extern "C" int mgcn_hatt_bwd_src_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                                      const int64_t *rowptr_t, const int32_t *col_t,
+                                      const int32_t *slot_map, const uint16_t *dY, int64_t lddy,
+                                      const float *alpha, const float *mask, float *dz,
+                                      const float *s_row, const float *s_col, int act,
+                                      int softmax, float temperature, const float *a,
+                                      const float *ds_dst, float *ds_src, uint16_t *dHp,
+                                      int64_t lddh, float *dHp_f32, void *stream) {
+  HardBwdSrcArgsT<BwdSrcArgsBf16> k{{{n_rows, H, C, act, softmax ? 1 : 0, rowptr_t, col_t,
+                                      slot_map, dY, lddy, alpha, mask, dz, s_row, s_col, a,
+                                      ds_dst, ds_src, dHp, lddh},
+                                     dHp_f32},
+                                    temperature};
+  return hatt_bwd_src("mgcn_hatt_bwd_src_bf16", k, nnz, stream);
 }
 
 extern "C" int mgcn_hatt_select(int64_t n_rows, int64_t nnz, int32_t H, const int64_t *rowptr,
@@ -292,18 +388,14 @@ extern "C" int mgcn_hatt_gather(int64_t n_rows, int64_t nnz, int32_t H, int32_t 
                                 const int64_t *rowptr, const int32_t *col, const float *alpha,
                                 const float *Hp, int64_t ldh, float *Y, int64_t ldy,
                                 void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE("mgcn_hatt_gather", n_rows, nnz, H, C);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hp && Y, "mgcn_hatt_gather: null array");
-  MGCN_REQUIRE(nnz == 0 || (col && alpha), "mgcn_hatt_gather: null col / alpha");
-  MGCN_REQUIRE(ldh >= (int64_t)H * C && ldy >= (int64_t)H * C,
-               "mgcn_hatt_gather: leading dimension too small");
-  GatherArgs k{n_rows, H, C, rowptr, col, alpha, Hp, ldh, Y, ldy};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL) \
-  hipLaunchKernelGGL((hatt_gather_kernel<FPL>), dim3(att_grid(n_rows)), dim3(kAttThreads), 0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("hatt_gather_kernel");
+  return hatt_gather<float>("mgcn_hatt_gather", n_rows, nnz, H, C, rowptr, col, alpha, Hp, ldh, Y,
+                            ldy, stream);
+}
+
+extern "C" int mgcn_hatt_gather_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                                     const int64_t *rowptr, const int32_t *col,
+                                     const float *alpha, const uint16_t *Hp, int64_t ldh,
+                                     uint16_t *Y, int64_t ldy, void *stream) {
+  return hatt_gather<uint16_t>("mgcn_hatt_gather_bf16", n_rows, nnz, H, C, rowptr, col, alpha, Hp,
+                               ldh, Y, ldy, stream);
 }

@@ -167,6 +167,28 @@ SIGNATURES = {
                                  _vp, _vp, _int, _int, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "mgcn_hatt_select": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
     "mgcn_hatt_gather": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    # bf16 feature rows: the fp32 entries' signatures (pointers are void *), the
+    # two bwd_src ones with the fp32 hand-off row before the stream, the fold
+    # with it before dHp
+    "mgcn_att_scores_bf16": (_int, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "mgcn_att_fwd_bf16": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp,
+                                 _i64, _vp, _i64, _vp, _vp]),
+    "mgcn_att_bwd_dst_bf16": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                     _vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "mgcn_att_bwd_src_bf16": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                     _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _i64, _vp,
+                                     _vp]),
+    "mgcn_att_dst_fold_bf16": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                      _vp]),
+    "mgcn_hatt_fwd_bf16": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _int, _vp, _f32, _vp,
+                                  _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "mgcn_hatt_bwd_dst_bf16": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                      _vp, _vp, _vp, _int, _int, _f32, _vp, _vp, _vp]),
+    "mgcn_hatt_bwd_src_bf16": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                      _vp, _vp, _vp, _int, _int, _f32, _vp, _vp, _vp, _vp, _i64,
+                                      _vp, _vp]),
+    "mgcn_hatt_gather_bf16": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
+                                     _vp]),
     "mgcn_gate_fwd": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _i64,
                              _int, _vp, _int, _vp, _i64, _vp, _vp, _vp]),
     "mgcn_gate_bwd_dst": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp,

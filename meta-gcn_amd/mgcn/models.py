@@ -354,6 +354,23 @@ class NodeModelGatedAdditive(NodeModelAdditive):
 
 
 # ------------------------------------------------------ graph_attention.py
+def _combine_heads(y, nheads, channels_1head, combine, bias):
+    """The head combine ('cat': none) and the bias after an attention op
+    (graph_attention.py:102-117).  bf16 rows (a bf16 ``x``): both are
+    accumulated in fp32 from the op's bf16 ``y`` and the result is rounded
+    once, so the output keeps the dtype of ``x`` whatever the bias's."""
+    rows = y.dtype
+    if rows != torch.float32 and (combine != 'cat' or bias is not None):
+        y = y.float()
+    if combine == 'add':
+        y = y.view(-1, nheads, channels_1head).sum(dim=1)
+    elif combine == 'mean':
+        y = y.view(-1, nheads, channels_1head).mean(dim=1)
+    if bias is not None:
+        y = y + bias
+    return y if y.dtype == rows else y.to(rows)
+
+
 class NodeModelAttention(NodeModelBase):
     """graph_attention.py:11-123: multi-head soft attention over a node's
     neighbourhood.  ``x @ W`` runs on :func:`mgcn.ops.linear`; scores, the
@@ -361,7 +378,9 @@ class NodeModelAttention(NodeModelBase):
     gather are :func:`mgcn.ops.attention_aggregate`.  As in the reference,
     deg_norm / edge_gate / aggr keep NodeModelBase's defaults and are unused,
     and with ``att_combine='cat'`` one head has out_channels / nheads channels
-    (else out_channels each)."""
+    (else out_channels each).  A bf16 ``x`` keeps bf16 rows through the op
+    (fp32 master parameters or a module after ``.to(torch.bfloat16)``) and
+    gives a bf16 output; fp32 is the reference's arithmetic."""
 
     def __init__(self, in_channels, out_channels, in_edgedim=None, nheads=1, att_act='none',
                  att_dropout=0, att_combine='cat', att_dir='in', bias=False, **kwargs):
@@ -409,12 +428,7 @@ class NodeModelAttention(NodeModelBase):
                 p=self.att_dropout.p, training=True)
         y, alpha = attention_aggregate(hp, self.att_weight, plan, self.nheads,
                                        self.att_act_name, self.att_dir, edge_mask=mask)
-        if self.att_combine == 'add':
-            y = y.view(-1, self.nheads, self.out_channels_1head).sum(dim=1)
-        elif self.att_combine == 'mean':
-            y = y.view(-1, self.nheads, self.out_channels_1head).mean(dim=1)
-        if self.bias is not None:
-            y = y + self.bias
+        y = _combine_heads(y, self.nheads, self.out_channels_1head, self.att_combine, self.bias)
         if attn_store is not None:
             attn_store.append(alpha)
         return y
@@ -507,12 +521,7 @@ class NodeModelHardAttention(NodeModelBase):
         y, alpha = hard_attention_aggregate(hp, self.att_weight, plan, self.nheads,
                                             self.att_act_name, self.att_dir, self.temperature,
                                             training=self.training, noise=noise, edge_mask=mask)
-        if self.att_combine == 'add':
-            y = y.view(-1, self.nheads, self.out_channels_1head).sum(dim=1)
-        elif self.att_combine == 'mean':
-            y = y.view(-1, self.nheads, self.out_channels_1head).mean(dim=1)
-        if self.bias is not None:
-            y = y + self.bias
+        y = _combine_heads(y, self.nheads, self.out_channels_1head, self.att_combine, self.bias)
         if attn_store is not None:
             attn_store.append(alpha)
         return y

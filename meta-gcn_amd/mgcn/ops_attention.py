@@ -1,6 +1,14 @@
 """Soft and hard multi-head attention over a graph plan on libmgcn's
 attention kernels.  Sits on :mod:`mgcn.ops_gemm` (the attention vector's
-gradient is one ``gemm_tn``); :mod:`mgcn.ops` re-exports every name."""
+gradient is one ``gemm_tn``); :mod:`mgcn.ops` re-exports every name.
+
+Feature rows are fp32 or bf16 (``Hp.dtype``).  A bf16 ``Hp`` takes the
+``mgcn_*_bf16`` sibling of every launch that reads or writes a feature row
+(timer names end in ``_bf16``): Hp, Y, dY and dHp are bf16, while the scores,
+alpha, the mask, the noise, dz, ds and the attention vector stay fp32.
+Contract ("bf16 attention rows"): every fp32 output has the bits of
+the fp32 path on ``Hp.float()`` / ``dY.float()``, every bf16 output those bits
+rounded once to nearest even."""
 from __future__ import annotations
 
 import torch
@@ -9,6 +17,85 @@ from . import _lib as L
 from ._call import _contig_f32, launch
 from .graph import GraphPlan
 from .ops_gemm import gemm_tn
+
+BF16 = torch.bfloat16
+
+
+def _require_row_dtype(t: torch.Tensor, name: str) -> None:
+    if t.dtype not in (torch.float32, BF16):
+        raise TypeError(f"{name} must be float32 or bfloat16, got {t.dtype}")
+
+
+def _rows(t: torch.Tensor, name: str) -> torch.Tensor:
+    """fp32 or bf16 [N, F] rows with unit column stride (any leading dimension
+    >= F, any offset: the bf16 kernels read and write single elements)."""
+    _require_row_dtype(t, name)
+    if t.dtype != BF16:
+        return _contig_f32(t, name)
+    if t.dim() != 2:
+        raise ValueError(f"{name} must be 2-D [N, F], got {tuple(t.shape)}")
+    if t.stride(1) != 1 or t.stride(0) < t.size(1):
+        t = t.contiguous()
+    return t
+
+
+def _grad_rows(dY: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """The incoming gradient in the row dtype of the forward."""
+    if dtype != BF16:
+        return _contig_f32(dY, "dY")
+    return _rows(dY.to(BF16), "dY")
+
+
+def _row_launch(lib, name: str, bf16: bool, dev, rows, edges, *args) -> None:
+    """One launch that touches feature rows: ``mgcn_<name>``, or for bf16 rows
+    its ``mgcn_<name>_bf16`` sibling, timed under the name without ``mgcn_``."""
+    if bf16:
+        name += "_bf16"
+    launch(name, "mgcn_" + name, dev, rows, edges, getattr(lib, "mgcn_" + name), *args)
+
+
+def _att_f32(att_weight: torch.Tensor, H: int, C: int) -> torch.Tensor:
+    """The attention vector as fp32 [H, 2C]; a bf16 one (a module after
+    ``.to(torch.bfloat16)``) is cast through autograd, so its gradient comes
+    back in its own dtype."""
+    if att_weight.dtype not in (torch.float32, BF16) or att_weight.numel() != 2 * H * C:
+        raise ValueError(f"att_weight must be float32 or bfloat16 [1, {H}, {2 * C}], got "
+                         f"{att_weight.dtype} {tuple(att_weight.shape)}")
+    return att_weight.reshape(H, 2 * C).to(torch.float32)
+
+
+def _datt(ds_src, ds_dst, Hp, H: int, C: int):
+    """da = [ds_src | ds_dst]^T Hp on mgcn_gemm_tn, of which head h's own C
+    columns are its rows; bf16 rows are upcast first (an fp32 temporary), so
+    the result is the fp32 path's bit for bit."""
+    full = gemm_tn(torch.cat([ds_src, ds_dst], dim=1), Hp.float() if Hp.dtype == BF16 else Hp)
+    full = full.view(2, H, H, C)  # [src | dst, head of ds, head of Hp, c]
+    hh = torch.arange(H, device=Hp.device)
+    return torch.cat([full[0, hh, hh], full[1, hh, hh]], dim=1)  # [H, 2C]
+
+
+def _bwd_src_fold(lib, hard_T, bf16, inn, plan, H, C, act, dY, alpha, mask, dz, s_src, s_dst, att,
+                  ds_dst, ds_src, st):
+    """mgcn_(h)att_bwd_src and, for 'out', mgcn_att_dst_fold: dHp in the row
+    dtype.  bf16 rows under 'out' hand the unrounded fp32 row from the first
+    launch to the second through a scratch [N, H C], so dHp is rounded once."""
+    dev = dY.device
+    N, nnz, HC = plan.num_nodes, plan.nnz, H * C
+    fwd, bwd = plan.fwd, plan.bwd
+    slot = plan.slot_map() if nnz else None
+    dHp = torch.empty(N, HC, dtype=dY.dtype, device=dev)
+    park = torch.empty(N, HC, dtype=torch.float32, device=dev) if bf16 and not inn else None
+    _row_launch(lib, "att_bwd_src" if hard_T is None else "hatt_bwd_src", bf16, dev, N, bwd.edges,
+                N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
+                dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
+                act, int(not inn), *(() if hard_T is None else (hard_T,)), L.ptr(att),
+                L.ptr(ds_dst) if inn else None, L.ptr(ds_src), L.ptr(dHp), HC,
+                *((L.ptr(park),) if bf16 else ()), st)
+    if not inn:
+        _row_launch(lib, "att_dst_fold", bf16, dev, N, fwd.edges,
+                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(dz), L.ptr(att), L.ptr(ds_dst),
+                    *((L.ptr(park),) if bf16 else ()), L.ptr(dHp), HC, st)
+    return dHp
 
 
 class _AttentionAggregate(torch.autograd.Function):
@@ -22,7 +109,9 @@ class _AttentionAggregate(torch.autograd.Function):
     dropout mask), the slot-order mask, s_src / s_dst.  Backward:
     mgcn_att_bwd_dst, mgcn_att_bwd_src (+ mgcn_att_dst_fold for 'out'), and the
     attention vector's gradient as one mgcn_gemm_tn ([ds_src | ds_dst]^T Hp,
-    of which head h's own C columns are its rows of da)."""
+    of which head h's own C columns are its rows of da).  bf16 ``Hp``: the
+    ``_bf16`` sibling of every launch but mgcn_edge_softmax; Y, the saved Hp
+    and dHp are bf16."""
 
     @staticmethod
     def forward(ctx, Hp, att, mask, plan: GraphPlan, H: int, act: int, att_dir: str):
@@ -32,27 +121,30 @@ class _AttentionAggregate(torch.autograd.Function):
         C = HC // H
         nnz = plan.nnz
         st = L.stream_of(dev)
+        bf = Hp.dtype == BF16
         att = att.detach().contiguous()
         s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
         s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        Y = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        Y = torch.empty(N, HC, dtype=Hp.dtype, device=dev)
         alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
         fwd, bwd = plan.fwd, plan.bwd
-        launch("att_scores", "mgcn_att_scores", dev, N, None, lib.mgcn_att_scores,
-               N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
+        _row_launch(lib, "att_scores", bf, dev, N, None,
+                    N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
         if att_dir == 'in' or nnz == 0:
-            launch("att_fwd", "mgcn_att_fwd", dev, N, fwd.edges, lib.mgcn_att_fwd,
-                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst), L.ptr(s_src),
-                   act, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, L.ptr(alpha), st)
+            _row_launch(lib, "att_fwd", bf, dev, N, fwd.edges,
+                        N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst),
+                        L.ptr(s_src), act, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y),
+                        HC, L.ptr(alpha), st)
         else:
             a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
             launch("edge_softmax", "mgcn_edge_softmax", dev, N, bwd.edges, lib.mgcn_edge_softmax,
                    N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
                    L.ptr(a_bwd), st)
             alpha[plan.slot_map()[:nnz].long()] = a_bwd
-            launch("att_fwd", "mgcn_att_fwd", dev, N, fwd.edges, lib.mgcn_att_fwd,
-                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act,
-                   L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None, st)
+            _row_launch(lib, "att_fwd", bf, dev, N, fwd.edges,
+                        N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act,
+                        L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None,
+                        st)
         ctx.plan, ctx.H, ctx.act, ctx.att_dir = plan, H, act, att_dir
         ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
         ctx.mark_non_differentiable(alpha)
@@ -68,33 +160,20 @@ class _AttentionAggregate(torch.autograd.Function):
         C = HC // H
         nnz = plan.nnz
         st = L.stream_of(dev)
-        dY = _contig_f32(dY, "dY")
-        fwd, bwd = plan.fwd, plan.bwd
-        slot = plan.slot_map() if nnz else None
+        bf = Hp.dtype == BF16
+        dY = _grad_rows(dY, Hp.dtype)
+        fwd = plan.fwd
         dz = torch.empty(nnz, H, dtype=torch.float32, device=dev)
         ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
         ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        dHp = torch.empty(N, HC, dtype=torch.float32, device=dev)
         inn = ctx.att_dir == 'in'
-        launch("att_bwd_dst", "mgcn_att_bwd_dst", dev, N, fwd.edges, lib.mgcn_att_bwd_dst,
-               N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
-               L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst), L.ptr(s_src),
-               act, int(inn), L.ptr(dz), L.ptr(ds_dst), st)
-        launch("att_bwd_src", "mgcn_att_bwd_src", dev, N, bwd.edges, lib.mgcn_att_bwd_src,
-               N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
-               dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
-               act, int(not inn), L.ptr(att), L.ptr(ds_dst) if inn else None, L.ptr(ds_src),
-               L.ptr(dHp), HC, st)
-        if not inn:
-            launch("att_dst_fold", "mgcn_att_dst_fold", dev, N, fwd.edges, lib.mgcn_att_dst_fold,
-                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(dz), L.ptr(att), L.ptr(ds_dst),
-                   L.ptr(dHp), HC, st)
-        datt = None
-        if ctx.needs_input_grad[1]:
-            full = gemm_tn(torch.cat([ds_src, ds_dst], dim=1), Hp)
-            full = full.view(2, H, H, C)  # [src | dst, head of ds, head of Hp, c]
-            hh = torch.arange(H, device=dev)
-            datt = torch.cat([full[0, hh, hh], full[1, hh, hh]], dim=1)  # [H, 2C]
+        _row_launch(lib, "att_bwd_dst", bf, dev, N, fwd.edges,
+                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
+                    L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst),
+                    L.ptr(s_src), act, int(inn), L.ptr(dz), L.ptr(ds_dst), st)
+        dHp = _bwd_src_fold(lib, None, bf, inn, plan, H, C, act, dY, alpha, mask, dz, s_src, s_dst,
+                            att, ds_dst, ds_src, st)
+        datt = _datt(ds_src, ds_dst, Hp, H, C) if ctx.needs_input_grad[1] else None
         return dHp, datt, None, None, None, None, None
 
 
@@ -112,23 +191,27 @@ def attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphP
 
     Returns ``(Y, alpha_coo)``: Y [N, H * C] = sum over in-edges of alpha' *
     Hp[src], and alpha' = alpha * mask as [E, H] in COO order, detached.
-    Differentiable in Hp and att_weight.  CPU tensors raise: no CPU path."""
+    Differentiable in Hp and att_weight.  CPU tensors raise: no CPU path.
+
+    ``Hp`` is float32 or bfloat16 (any other dtype: ``TypeError``).  For a
+    bfloat16 ``Hp`` the feature rows stay bf16 through every kernel and Y and
+    the gradient of Hp are bf16; alpha stays fp32.  ``att_weight`` may be
+    float32 or bfloat16 with either (its gradient has its dtype)."""
+    _require_row_dtype(Hp, "Hp")
     L.require_device(Hp, att_weight, plan.fwd.rowptr, edge_mask)
     if act not in L.ATT_ACT_CODES:
         raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
     if att_dir not in ('in', 'out'):
         raise ValueError(f"att_dir must be 'in' or 'out', got {att_dir!r}")
     H = int(nheads)
-    Hp2 = _contig_f32(Hp.reshape(Hp.size(0), -1), "Hp")
+    Hp2 = _rows(Hp.reshape(Hp.size(0), -1), "Hp")
     if Hp2.size(0) != plan.num_nodes:
         raise ValueError(f"Hp has {Hp2.size(0)} rows, graph has {plan.num_nodes} nodes")
     HC = Hp2.size(1)
     if H < 1 or HC % H:
         raise ValueError(f"Hp width {HC} is not a multiple of nheads = {H}")
     C = HC // H
-    if att_weight.dtype != torch.float32 or att_weight.numel() != 2 * HC:
-        raise ValueError(f"att_weight must be float32 [1, {H}, {2 * C}], got "
-                         f"{att_weight.dtype} {tuple(att_weight.shape)}")
+    att2 = _att_f32(att_weight, H, C)
     if not (1 <= H <= 16 and HC <= 1024 and plan.nnz * H < 2 ** 31):
         raise L.MgcnError(f"attention_aggregate: unsupported shape (H = {H}, C = {C}, nnz = "
                           f"{plan.nnz}): need 1 <= H <= 16, H C <= 1024, nnz H < 2^31")
@@ -138,8 +221,7 @@ def attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphP
             raise ValueError(f"edge_mask must be [{plan.nnz}, {H}] in COO order, got "
                              f"{tuple(edge_mask.shape)}")
         mask = edge_mask.detach().to(torch.float32)[plan.fwd.eid.long()].contiguous()
-    Y, alpha = _AttentionAggregate.apply(Hp2, att_weight.reshape(H, 2 * C), mask, plan, H,
-                                         L.ATT_ACT_CODES[act], att_dir)
+    Y, alpha = _AttentionAggregate.apply(Hp2, att2, mask, plan, H, L.ATT_ACT_CODES[act], att_dir)
     alpha = alpha.detach()
     alpha_coo = torch.empty_like(alpha)
     if plan.nnz:
@@ -165,19 +247,20 @@ class _HardAttentionTrain(torch.autograd.Function):
         C = HC // H
         nnz = plan.nnz
         st = L.stream_of(dev)
+        bf = Hp.dtype == BF16
         att = att.detach().contiguous()
         s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
         s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        Y = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        Y = torch.empty(N, HC, dtype=Hp.dtype, device=dev)
         alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
         fwd, bwd = plan.fwd, plan.bwd
-        launch("att_scores", "mgcn_att_scores", dev, N, None, lib.mgcn_att_scores,
-               N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
+        _row_launch(lib, "att_scores", bf, dev, N, None,
+                    N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
         if att_dir == 'in' or nnz == 0:
-            launch("hatt_fwd", "mgcn_hatt_fwd", dev, N, fwd.edges, lib.mgcn_hatt_fwd,
-                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst), L.ptr(s_src),
-                   act, L.ptr(noise), T, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y),
-                   HC, L.ptr(alpha), st)
+            _row_launch(lib, "hatt_fwd", bf, dev, N, fwd.edges,
+                        N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst),
+                        L.ptr(s_src), act, L.ptr(noise), T, None, L.ptr(mask), L.ptr(Hp),
+                        Hp.stride(0), L.ptr(Y), HC, L.ptr(alpha), st)
         else:
             a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
             launch("hatt_edge_softmax", "mgcn_hatt_edge_softmax", dev, N, bwd.edges,
@@ -185,9 +268,10 @@ class _HardAttentionTrain(torch.autograd.Function):
                    N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
                    L.ptr(noise), T, L.ptr(a_bwd), st)
             alpha[plan.slot_map()[:nnz].long()] = a_bwd
-            launch("hatt_fwd", "mgcn_hatt_fwd", dev, N, fwd.edges, lib.mgcn_hatt_fwd,
-                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act, None, T,
-                   L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None, st)
+            _row_launch(lib, "hatt_fwd", bf, dev, N, fwd.edges,
+                        N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act, None, T,
+                        L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None,
+                        st)
         ctx.plan, ctx.H, ctx.act, ctx.att_dir, ctx.T = plan, H, act, att_dir, T
         ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
         ctx.mark_non_differentiable(alpha)
@@ -203,33 +287,20 @@ class _HardAttentionTrain(torch.autograd.Function):
         C = HC // H
         nnz = plan.nnz
         st = L.stream_of(dev)
-        dY = _contig_f32(dY, "dY")
-        fwd, bwd = plan.fwd, plan.bwd
-        slot = plan.slot_map() if nnz else None
+        bf = Hp.dtype == BF16
+        dY = _grad_rows(dY, Hp.dtype)
+        fwd = plan.fwd
         dz = torch.empty(nnz, H, dtype=torch.float32, device=dev)
         ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
         ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        dHp = torch.empty(N, HC, dtype=torch.float32, device=dev)
         inn = ctx.att_dir == 'in'
-        launch("hatt_bwd_dst", "mgcn_hatt_bwd_dst", dev, N, fwd.edges, lib.mgcn_hatt_bwd_dst,
-               N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
-               L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst), L.ptr(s_src),
-               act, int(inn), T, L.ptr(dz), L.ptr(ds_dst), st)
-        launch("hatt_bwd_src", "mgcn_hatt_bwd_src", dev, N, bwd.edges, lib.mgcn_hatt_bwd_src,
-               N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
-               dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
-               act, int(not inn), T, L.ptr(att), L.ptr(ds_dst) if inn else None, L.ptr(ds_src),
-               L.ptr(dHp), HC, st)
-        if not inn:
-            launch("att_dst_fold", "mgcn_att_dst_fold", dev, N, fwd.edges, lib.mgcn_att_dst_fold,
-                   N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(dz), L.ptr(att), L.ptr(ds_dst),
-                   L.ptr(dHp), HC, st)
-        datt = None
-        if ctx.needs_input_grad[1]:
-            full = gemm_tn(torch.cat([ds_src, ds_dst], dim=1), Hp)
-            full = full.view(2, H, H, C)  # [src | dst, head of ds, head of Hp, c]
-            hh = torch.arange(H, device=dev)
-            datt = torch.cat([full[0, hh, hh], full[1, hh, hh]], dim=1)  # [H, 2C]
+        _row_launch(lib, "hatt_bwd_dst", bf, dev, N, fwd.edges,
+                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
+                    L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst),
+                    L.ptr(s_src), act, int(inn), T, L.ptr(dz), L.ptr(ds_dst), st)
+        dHp = _bwd_src_fold(lib, T, bf, inn, plan, H, C, act, dY, alpha, mask, dz, s_src, s_dst,
+                            att, ds_dst, ds_src, st)
+        datt = _datt(ds_src, ds_dst, Hp, H, C) if ctx.needs_input_grad[1] else None
         return dHp, datt, None, None, None, None, None, None, None
 
 
@@ -253,15 +324,16 @@ class _HardAttentionEval(torch.autograd.Function):
         C = HC // H
         nnz = plan.nnz
         st = L.stream_of(dev)
+        bf = Hp.dtype == BF16
         att = att.detach().contiguous()
         s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
         s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        Y = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        Y = torch.empty(N, HC, dtype=Hp.dtype, device=dev)
         alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
         winner = torch.empty(N, H, dtype=torch.int32, device=dev)
         fwd, bwd = plan.fwd, plan.bwd
-        launch("att_scores", "mgcn_att_scores", dev, N, None, lib.mgcn_att_scores,
-               N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
+        _row_launch(lib, "att_scores", bf, dev, N, None,
+                    N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
         if att_dir == 'in':
             launch("hatt_select", "mgcn_hatt_select", dev, N, fwd.edges, lib.mgcn_hatt_select,
                    N, nnz, H, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst), L.ptr(s_src), act,
@@ -280,10 +352,10 @@ class _HardAttentionEval(torch.autograd.Function):
             mark = (winner < 0).any(dim=0).roll(-1).to(torch.float32)
             last = plan.last_edge_slot()  # cached on the plan: no scan, no host sync
             alpha[last] = torch.maximum(alpha[last], mark)
-        launch("hatt_gather", "mgcn_hatt_gather", dev, N, fwd.edges, lib.mgcn_hatt_gather,
-               N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(alpha), L.ptr(Hp),
-               Hp.stride(0), L.ptr(Y), HC, st)
-        ctx.plan, ctx.H = plan, H
+        _row_launch(lib, "hatt_gather", bf, dev, N, fwd.edges,
+                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(alpha), L.ptr(Hp),
+                    Hp.stride(0), L.ptr(Y), HC, st)
+        ctx.plan, ctx.H, ctx.row_dtype = plan, H, Hp.dtype
         ctx.save_for_backward(alpha, att)
         ctx.mark_non_differentiable(alpha)
         return Y, alpha
@@ -295,17 +367,19 @@ class _HardAttentionEval(torch.autograd.Function):
         lib = L.load()
         dev = alpha.device
         N, nnz = plan.num_nodes, plan.nnz
-        dY = _contig_f32(dY, "dY")
+        bf = ctx.row_dtype == BF16
+        dY = _grad_rows(dY, ctx.row_dtype)
         HC = dY.size(1)
         bwd = plan.bwd
         slot = plan.slot_map() if nnz else None
         dz = torch.zeros(nnz, H, dtype=torch.float32, device=dev)
         ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        dHp = torch.empty(N, HC, dtype=torch.float32, device=dev)
-        launch("att_bwd_src", "mgcn_att_bwd_src", dev, N, bwd.edges, lib.mgcn_att_bwd_src,
-               N, nnz, H, HC // H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
-               dY.stride(0), L.ptr(alpha), None, L.ptr(dz), None, None, 0, 0, L.ptr(att), None,
-               L.ptr(ds_src), L.ptr(dHp), HC, L.stream_of(dev))
+        dHp = torch.empty(N, HC, dtype=dY.dtype, device=dev)
+        _row_launch(lib, "att_bwd_src", bf, dev, N, bwd.edges,
+                    N, nnz, H, HC // H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
+                    dY.stride(0), L.ptr(alpha), None, L.ptr(dz), None, None, 0, 0, L.ptr(att),
+                    None, L.ptr(ds_src), L.ptr(dHp), HC, *((None,) if bf else ()),
+                    L.stream_of(dev))
         return dHp, None, None, None, None, None, None
 
 
@@ -331,23 +405,23 @@ def hard_attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: G
     ``edge_mask`` is not used (the reference drops out in training alone).
 
     Returns ``(Y, alpha_coo)``: Y [N, H * C] and the coefficients that weighted
-    the messages, [E, H] in COO order, detached."""
+    the messages, [E, H] in COO order, detached.  ``Hp`` float32 or bfloat16 as
+    for :func:`attention_aggregate`."""
+    _require_row_dtype(Hp, "Hp")
     L.require_device(Hp, att_weight, plan.fwd.rowptr, edge_mask, noise)
     if act not in L.ATT_ACT_CODES:
         raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
     if att_dir not in ('in', 'out'):
         raise ValueError(f"att_dir must be 'in' or 'out', got {att_dir!r}")
     H = int(nheads)
-    Hp2 = _contig_f32(Hp.reshape(Hp.size(0), -1), "Hp")
+    Hp2 = _rows(Hp.reshape(Hp.size(0), -1), "Hp")
     if Hp2.size(0) != plan.num_nodes:
         raise ValueError(f"Hp has {Hp2.size(0)} rows, graph has {plan.num_nodes} nodes")
     HC = Hp2.size(1)
     if H < 1 or HC % H:
         raise ValueError(f"Hp width {HC} is not a multiple of nheads = {H}")
     C = HC // H
-    if att_weight.dtype != torch.float32 or att_weight.numel() != 2 * HC:
-        raise ValueError(f"att_weight must be float32 [1, {H}, {2 * C}], got "
-                         f"{att_weight.dtype} {tuple(att_weight.shape)}")
+    att2 = _att_f32(att_weight, H, C)
     if not (1 <= H <= 16 and HC <= 1024 and plan.nnz * H < 2 ** 31):
         raise L.MgcnError(f"hard_attention_aggregate: unsupported shape (H = {H}, C = {C}, nnz = "
                           f"{plan.nnz}): need 1 <= H <= 16, H C <= 1024, nnz H < 2^31")
@@ -361,7 +435,6 @@ def hard_attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: G
             raise ValueError(f"noise must be [{plan.nnz}, {H}] in COO order, got "
                              f"{tuple(noise.shape)}")
         noise = noise.detach().to(torch.float32)[walked.eid.long()].contiguous()
-    att2 = att_weight.reshape(H, 2 * C)
     mask = None
     if training:
         if edge_mask is not None:
