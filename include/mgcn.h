@@ -1221,6 +1221,51 @@ int mgcn_gate_bwd_src(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *row
                       const float *dl, const uint32_t *win_mask, const float *w_sd,
                       const float *dc, float *da, float *dHx, int64_t lddh, void *stream);
 
+/*
+ * The three gate launches with the row schedule of the view they walk
+ * (mgcn_row_schedule: order, n_heavy, n_giant; the fwd view's for
+ * mgcn_gate_fwd_sched / mgcn_gate_bwd_dst_sched, the bwd view's for
+ * mgcn_gate_bwd_src_sched).  Backward-compatible additions: MGCN_ABI_VERSION
+ * stays 22.  The rows order[0, n_heavy) -- a hub of several thousand edges
+ * would hold one wave for the whole launch -- go to workgroups: forward and
+ * adjoint by source one workgroup per row (the SpMM's heavy-row body over a
+ * per-slot coefficient g w; the first n_giant rows by the larger workgroup),
+ * adjoint by destination one wave per 64-slot chunk of the row, then one wave
+ * per row for dc.  The rows order[n_heavy, n_rows) stay on the wave-per-row
+ * kernels.  Every output element has the bits the entry without a schedule
+ * gives it; no atomics.  All launches are on `stream`.
+ *
+ * coef is the caller's scratch of nnz floats (g w of every slot of a heavy
+ * row, in the slot order of the view walked; its contents after the call are
+ * unspecified); required whenever order is given and nnz > 0.  The adjoint
+ * by destination needs none.  order == NULL: exactly the entry without a
+ * schedule (n_heavy, n_giant and coef are not read).  With order given,
+ * 0 <= n_giant <= n_heavy <= n_rows, else MGCN_EINVAL; like every other
+ * argument error, before any launch.  order holds each row of [0, n_rows)
+ * once; a row range of a view cannot carry a schedule.
+ */
+int mgcn_gate_fwd_sched(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
+                        const int32_t *col, const int32_t *eid, const float *a, const float *c,
+                        const float *t, int t_bcast, const float *w, const float *Hx,
+                        int64_t ldh, int reduce, const float *bias, int relu, float *Y,
+                        int64_t ldy, float *g, int32_t *argmax, const int32_t *order,
+                        int64_t n_heavy, int64_t n_giant, float *coef, void *stream);
+
+int mgcn_gate_bwd_dst_sched(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
+                            const int32_t *col, const float *Hx, int64_t ldh, const float *dY,
+                            int64_t lddy, const float *w, const float *g,
+                            const uint32_t *win_mask, const float *dg_in, float *dl, float *dc,
+                            float *dw, const int32_t *order, int64_t n_heavy, int64_t n_giant,
+                            void *stream);
+
+int mgcn_gate_bwd_src_sched(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr_t,
+                            const int32_t *col_t, const int32_t *slot_map, const float *dY,
+                            int64_t lddy, const float *w_t, const float *row_scale,
+                            const float *g, const float *dl, const uint32_t *win_mask,
+                            const float *w_sd, const float *dc, float *da, float *dHx,
+                            int64_t lddh, const int32_t *order, int64_t n_heavy,
+                            int64_t n_giant, float *coef, void *stream);
+
 /* --------------------------------------------------- multi-kernel layers */
 
 /*

@@ -18,47 +18,24 @@
 // comes from the lane that formed it (ds_bpermute).  No LDS, no barrier, no
 // atomics; slots keep COO order and every sum has a fixed order (per-slot dot
 // products: the lane's own products in i order, then the xor butterfly), so
-// results are bitwise repeatable.
+// results are bitwise repeatable.  With a row schedule (the mgcn_gate_*_sched
+// entries) the rows over 128 edges go to workgroups instead
+// (edge_gate_heavy.hip), with the same bits; these kernels then walk the
+// schedule's remaining rows.
 //
 // Roofline (forward): 8 (N + 1) rowptr + nnz (4 col + 4 C row + 4 a + 4 g
 // [+ 4 w] [+ 4 t]) + 4 N C (Y) + 4 N (c) bytes.
 
 #include "attention.h"
+#include "edge_gate.h"
 
 namespace mgcn {
 namespace {
 
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = __fadd_rn(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-__device__ inline float gate_sigmoid(float l) {
-  return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-l)));
-}
-
-// bit f of a slot's winner words (mgcn_max_mask layout: [nnz, ceil(C / 32)])
-__device__ inline bool won(const uint32_t *win, int64_t slot, int W, int f) {
-  return (win[slot * W + (f >> 5)] >> (f & 31)) & 1u;
-}
-
 // ----------------------------------------------------------------- forward
-struct GateFwdArgs {
-  int64_t n_rows;
-  int C, reduce, relu, t_bcast;
-  const int64_t *rowptr;
-  const int32_t *col, *eid;
-  const float *a, *c, *t, *w, *Hx;
-  int64_t ldh;
-  const float *bias;
-  float *Y;
-  int64_t ldy;
-  float *g;
-  int32_t *argmax;
-};
-
-template <int FPL, bool MAX>
+// SCHED: the rows order[n_heavy, n_rows) of the schedule (the heavy rows are
+// edge_gate_heavy.hip's); else rows 0 .. n_rows
+template <int FPL, bool MAX, bool SCHED = false>
 __global__ __launch_bounds__(kAttThreads) void gate_fwd_kernel(GateFwdArgs a) {
   constexpr int U = gather_unroll<FPL>();
   const int lane = threadIdx.x & 63;
@@ -66,7 +43,9 @@ __global__ __launch_bounds__(kAttThreads) void gate_fwd_kernel(GateFwdArgs a) {
   const int64_t nwaves = (int64_t)gridDim.x * kAttWaves;
   const int C = a.C;
   const float tb = (a.t != nullptr && a.t_bcast) ? a.t[0] : 0.0f;
-  for (int64_t row = wave0; row < a.n_rows; row += nwaves) {
+  const int64_t n_work = SCHED ? a.n_rows - a.s.n_heavy : a.n_rows;
+  for (int64_t ri = wave0; ri < n_work; ri += nwaves) {
+    const int64_t row = SCHED ? (int64_t)a.s.order[a.s.n_heavy + ri] : ri;
     const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
     const float cr = a.c != nullptr ? a.c[row] : 0.0f;
     float acc[FPL];
@@ -144,28 +123,16 @@ __global__ __launch_bounds__(kAttThreads) void gate_fwd_kernel(GateFwdArgs a) {
 }
 
 // ------------------------------------------------- adjoint, by destination
-struct GateBwdDstArgs {
-  int64_t n_rows;
-  int C;
-  const int64_t *rowptr;
-  const int32_t *col;
-  const float *Hx;
-  int64_t ldh;
-  const float *dY;
-  int64_t lddy;
-  const float *w, *g, *dg_in;
-  const uint32_t *win;
-  float *dl, *dc, *dw;
-};
-
-template <int FPL, bool MAX>
+template <int FPL, bool MAX, bool SCHED = false>
 __global__ __launch_bounds__(kAttThreads) void gate_bwd_dst_kernel(GateBwdDstArgs a) {
   constexpr int U = gather_unroll<FPL>();
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = blockIdx.x * (int64_t)kAttWaves + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kAttWaves;
   const int C = a.C, W = (a.C + 31) >> 5;
-  for (int64_t row = wave0; row < a.n_rows; row += nwaves) {
+  const int64_t n_work = SCHED ? a.n_rows - a.s.n_heavy : a.n_rows;
+  for (int64_t ri = wave0; ri < n_work; ri += nwaves) {
+    const int64_t row = SCHED ? (int64_t)a.s.order[a.s.n_heavy + ri] : ri;
     float dy[FPL];
 #pragma unroll
     for (int i = 0; i < FPL; ++i) {
@@ -221,28 +188,16 @@ __global__ __launch_bounds__(kAttThreads) void gate_bwd_dst_kernel(GateBwdDstArg
 }
 
 // ------------------------------------------------------ adjoint, by source
-struct GateBwdSrcArgs {
-  int64_t n_rows;
-  int C;
-  const int64_t *rowptr;
-  const int32_t *col, *slot;
-  const float *dY;
-  int64_t lddy;
-  const float *w_t, *row_scale, *g, *dl;
-  const uint32_t *win;
-  const float *wsd, *dc;
-  float *da, *dHx;
-  int64_t lddh;
-};
-
-template <int FPL, bool MAX>
+template <int FPL, bool MAX, bool SCHED = false>
 __global__ __launch_bounds__(kAttThreads) void gate_bwd_src_kernel(GateBwdSrcArgs a) {
   constexpr int U = gather_unroll<FPL>();
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = blockIdx.x * (int64_t)kAttWaves + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kAttWaves;
   const int C = a.C, W = (a.C + 31) >> 5;
-  for (int64_t row = wave0; row < a.n_rows; row += nwaves) {
+  const int64_t n_work = SCHED ? a.n_rows - a.s.n_heavy : a.n_rows;
+  for (int64_t ri = wave0; ri < n_work; ri += nwaves) {
+    const int64_t row = SCHED ? (int64_t)a.s.order[a.s.n_heavy + ri] : ri;
     const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
     float acc[FPL];
 #pragma unroll
@@ -313,12 +268,71 @@ __global__ __launch_bounds__(kAttThreads) void gate_bwd_src_kernel(GateBwdSrcArg
 
 using namespace mgcn;
 
-#define GATE_REQUIRE_SHAPE(fn, n_rows, nnz, C)                                          \
-  do {                                                                                  \
-    MGCN_REQUIRE((n_rows) >= 0 && (nnz) >= 0, fn ": negative size");                    \
-    MGCN_REQUIRE((C) >= 1 && (C) <= 1024, fn ": need 1 <= C <= 1024 (C = %d)", (int)(C)); \
-    MGCN_REQUIRE((int64_t)(nnz) < ((int64_t)1 << 31), fn ": need nnz < 2^31");           \
+#define GATE_REQUIRE_SHAPE(fn, n_rows, nnz, C)                                                 \
+  do {                                                                                         \
+    MGCN_REQUIRE((n_rows) >= 0 && (nnz) >= 0, "%s: negative size", fn);                        \
+    MGCN_REQUIRE((C) >= 1 && (C) <= 1024, "%s: need 1 <= C <= 1024 (C = %d)", fn, (int)(C));   \
+    MGCN_REQUIRE((int64_t)(nnz) < ((int64_t)1 << 31), "%s: need nnz < 2^31", fn);              \
   } while (0)
+
+// the schedule of a _sched entry (order == NULL: none, the counts are not read)
+#define GATE_REQUIRE_SCHED(fn, s, n_rows)                                                      \
+  MGCN_REQUIRE((s).order == nullptr ||                                                         \
+                   (0 <= (s).n_giant && (s).n_giant <= (s).n_heavy && (s).n_heavy <= (n_rows)), \
+               "%s: need 0 <= n_giant <= n_heavy <= n_rows", fn)
+
+// one wave kernel over rows 0 .. n_rows (sched false) or over the schedule's
+// rows past the heavy ones
+#define GATE_LAUNCH(KERNEL, FPL, is_max, sched, n_work, st, k)                                 \
+  do {                                                                                         \
+    const dim3 grid_(att_grid(n_work)), block_(kAttThreads);                                   \
+    if ((is_max) && (sched))                                                                   \
+      hipLaunchKernelGGL((KERNEL<FPL, true, true>), grid_, block_, 0, st, k);                  \
+    else if (is_max)                                                                           \
+      hipLaunchKernelGGL((KERNEL<FPL, true, false>), grid_, block_, 0, st, k);                 \
+    else if (sched)                                                                            \
+      hipLaunchKernelGGL((KERNEL<FPL, false, true>), grid_, block_, 0, st, k);                 \
+    else                                                                                       \
+      hipLaunchKernelGGL((KERNEL<FPL, false, false>), grid_, block_, 0, st, k);                \
+  } while (0)
+
+// The body of mgcn_gate_fwd (s.order == NULL: its launch, nothing else) and of
+// mgcn_gate_fwd_sched: the heavy rows by workgroups, then the wave kernel over
+// the rest.
+static int gate_fwd_run(const char *fn, int64_t n_rows, int64_t nnz, int32_t C,
+                        const int64_t *rowptr, const int32_t *col, const int32_t *eid,
+                        const float *a, const float *c, const float *t, int t_bcast,
+                        const float *w, const float *Hx, int64_t ldh, int reduce,
+                        const float *bias, int relu, float *Y, int64_t ldy, float *g,
+                        int32_t *argmax, GateSched s, void *stream) {
+  clear_error();
+  GATE_REQUIRE_SHAPE(fn, n_rows, nnz, C);
+  MGCN_REQUIRE(reduce == MGCN_REDUCE_SUM || reduce == MGCN_REDUCE_MEAN ||
+                   reduce == MGCN_REDUCE_MAX, "%s: bad reduce %d", fn, reduce);
+  GATE_REQUIRE_SCHED(fn, s, n_rows);
+  if (n_rows == 0) return MGCN_OK;
+  MGCN_REQUIRE(rowptr && Hx && Y, "%s: null array", fn);
+  MGCN_REQUIRE(nnz == 0 || (col && g), "%s: null col / g", fn);
+  MGCN_REQUIRE(reduce != MGCN_REDUCE_MAX || (argmax && (eid || nnz == 0)),
+               "%s: MAX needs argmax and eid", fn);
+  MGCN_REQUIRE(ldh >= C && ldy >= C, "%s: leading dimension too small", fn);
+  MGCN_REQUIRE(s.order == nullptr || nnz == 0 || s.coef,
+               "%s: a schedule needs the coef scratch [nnz]", fn);
+  const bool sched = s.order != nullptr;
+  if (!sched) s = GateSched{};
+  GateFwdArgs k{n_rows, C, reduce, relu ? 1 : 0, t_bcast ? 1 : 0, rowptr, col, eid, a, c, t, w,
+                Hx, ldh, bias, Y, ldy, g, argmax, s};
+  hipStream_t st = as_stream(stream);
+  if (s.n_heavy > 0)
+    if (int rc = gate_fwd_heavy(k, st)) return rc;
+  const int64_t n_work = n_rows - s.n_heavy;
+  if (n_work == 0) return MGCN_OK;
+  const bool is_max = reduce == MGCN_REDUCE_MAX;
+#define CALL(FPL) GATE_LAUNCH(gate_fwd_kernel, FPL, is_max, sched, n_work, st, k)
+  ATT_DISPATCH(C, CALL);
+#undef CALL
+  return check_launch("gate_fwd_kernel");
+}
 
 extern "C" int mgcn_gate_fwd(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
                              const int32_t *col, const int32_t *eid, const float *a,
@@ -326,31 +340,47 @@ extern "C" int mgcn_gate_fwd(int64_t n_rows, int64_t nnz, int32_t C, const int64
                              const float *Hx, int64_t ldh, int reduce, const float *bias,
                              int relu, float *Y, int64_t ldy, float *g, int32_t *argmax,
                              void *stream) {
+  return gate_fwd_run("mgcn_gate_fwd", n_rows, nnz, C, rowptr, col, eid, a, c, t, t_bcast, w, Hx,
+                      ldh, reduce, bias, relu, Y, ldy, g, argmax, GateSched{}, stream);
+}
+
+extern "C" int mgcn_gate_fwd_sched(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
+                                   const int32_t *col, const int32_t *eid, const float *a,
+                                   const float *c, const float *t, int t_bcast, const float *w,
+                                   const float *Hx, int64_t ldh, int reduce, const float *bias,
+                                   int relu, float *Y, int64_t ldy, float *g, int32_t *argmax,
+                                   const int32_t *order, int64_t n_heavy, int64_t n_giant,
+                                   float *coef, void *stream) {
+  return gate_fwd_run("mgcn_gate_fwd_sched", n_rows, nnz, C, rowptr, col, eid, a, c, t, t_bcast,
+                      w, Hx, ldh, reduce, bias, relu, Y, ldy, g, argmax,
+                      GateSched{order, n_heavy, n_giant, coef}, stream);
+}
+
+static int gate_bwd_dst_run(const char *fn, int64_t n_rows, int64_t nnz, int32_t C,
+                            const int64_t *rowptr, const int32_t *col, const float *Hx,
+                            int64_t ldh, const float *dY, int64_t lddy, const float *w,
+                            const float *g, const uint32_t *win_mask, const float *dg_in,
+                            float *dl, float *dc, float *dw, GateSched s, void *stream) {
   clear_error();
-  GATE_REQUIRE_SHAPE("mgcn_gate_fwd", n_rows, nnz, C);
-  MGCN_REQUIRE(reduce == MGCN_REDUCE_SUM || reduce == MGCN_REDUCE_MEAN ||
-                   reduce == MGCN_REDUCE_MAX, "mgcn_gate_fwd: bad reduce %d", reduce);
+  GATE_REQUIRE_SHAPE(fn, n_rows, nnz, C);
+  GATE_REQUIRE_SCHED(fn, s, n_rows);
   if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hx && Y, "mgcn_gate_fwd: null array");
-  MGCN_REQUIRE(nnz == 0 || (col && g), "mgcn_gate_fwd: null col / g");
-  MGCN_REQUIRE(reduce != MGCN_REDUCE_MAX || (argmax && (eid || nnz == 0)),
-               "mgcn_gate_fwd: MAX needs argmax and eid");
-  MGCN_REQUIRE(ldh >= C && ldy >= C, "mgcn_gate_fwd: leading dimension too small");
-  GateFwdArgs k{n_rows, C, reduce, relu ? 1 : 0, t_bcast ? 1 : 0, rowptr, col, eid, a, c, t, w,
-                Hx, ldh, bias, Y, ldy, g, argmax};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                             \
-  do {                                                                                        \
-    if (reduce == MGCN_REDUCE_MAX)                                                            \
-      hipLaunchKernelGGL((gate_fwd_kernel<FPL, true>), dim3(att_grid(n_rows)),                \
-                         dim3(kAttThreads), 0, s, k);                                         \
-    else                                                                                      \
-      hipLaunchKernelGGL((gate_fwd_kernel<FPL, false>), dim3(att_grid(n_rows)),               \
-                         dim3(kAttThreads), 0, s, k);                                         \
-  } while (0)
+  MGCN_REQUIRE(rowptr && Hx && dY, "%s: null array", fn);
+  MGCN_REQUIRE(nnz == 0 || (col && g && dl), "%s: null col / g / dl", fn);
+  MGCN_REQUIRE(ldh >= C && lddy >= C, "%s: leading dimension too small", fn);
+  const bool sched = s.order != nullptr;
+  if (!sched) s = GateSched{};
+  GateBwdDstArgs k{n_rows, C, rowptr, col, Hx, ldh, dY, lddy, w, g, dg_in, win_mask, dl, dc, dw, s};
+  hipStream_t st = as_stream(stream);
+  if (s.n_heavy > 0)
+    if (int rc = gate_bwd_dst_heavy(k, st)) return rc;
+  const int64_t n_work = n_rows - s.n_heavy;
+  if (n_work == 0) return MGCN_OK;
+  const bool is_max = win_mask != nullptr;
+#define CALL(FPL) GATE_LAUNCH(gate_bwd_dst_kernel, FPL, is_max, sched, n_work, st, k)
   ATT_DISPATCH(C, CALL);
 #undef CALL
-  return check_launch("gate_fwd_kernel");
+  return check_launch("gate_bwd_dst_kernel");
 }
 
 extern "C" int mgcn_gate_bwd_dst(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
@@ -358,26 +388,54 @@ extern "C" int mgcn_gate_bwd_dst(int64_t n_rows, int64_t nnz, int32_t C, const i
                                  const float *dY, int64_t lddy, const float *w, const float *g,
                                  const uint32_t *win_mask, const float *dg_in, float *dl,
                                  float *dc, float *dw, void *stream) {
+  return gate_bwd_dst_run("mgcn_gate_bwd_dst", n_rows, nnz, C, rowptr, col, Hx, ldh, dY, lddy, w,
+                          g, win_mask, dg_in, dl, dc, dw, GateSched{}, stream);
+}
+
+extern "C" int mgcn_gate_bwd_dst_sched(int64_t n_rows, int64_t nnz, int32_t C,
+                                       const int64_t *rowptr, const int32_t *col, const float *Hx,
+                                       int64_t ldh, const float *dY, int64_t lddy, const float *w,
+                                       const float *g, const uint32_t *win_mask,
+                                       const float *dg_in, float *dl, float *dc, float *dw,
+                                       const int32_t *order, int64_t n_heavy, int64_t n_giant,
+                                       void *stream) {
+  return gate_bwd_dst_run("mgcn_gate_bwd_dst_sched", n_rows, nnz, C, rowptr, col, Hx, ldh, dY,
+                          lddy, w, g, win_mask, dg_in, dl, dc, dw,
+                          GateSched{order, n_heavy, n_giant, nullptr}, stream);
+}
+
+static int gate_bwd_src_run(const char *fn, int64_t n_rows, int64_t nnz, int32_t C,
+                            const int64_t *rowptr_t, const int32_t *col_t,
+                            const int32_t *slot_map, const float *dY, int64_t lddy,
+                            const float *w_t, const float *row_scale, const float *g,
+                            const float *dl, const uint32_t *win_mask, const float *w_sd,
+                            const float *dc, float *da, float *dHx, int64_t lddh, GateSched s,
+                            void *stream) {
   clear_error();
-  GATE_REQUIRE_SHAPE("mgcn_gate_bwd_dst", n_rows, nnz, C);
+  GATE_REQUIRE_SHAPE(fn, n_rows, nnz, C);
+  GATE_REQUIRE_SCHED(fn, s, n_rows);
   if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hx && dY, "mgcn_gate_bwd_dst: null array");
-  MGCN_REQUIRE(nnz == 0 || (col && g && dl), "mgcn_gate_bwd_dst: null col / g / dl");
-  MGCN_REQUIRE(ldh >= C && lddy >= C, "mgcn_gate_bwd_dst: leading dimension too small");
-  GateBwdDstArgs k{n_rows, C, rowptr, col, Hx, ldh, dY, lddy, w, g, dg_in, win_mask, dl, dc, dw};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                             \
-  do {                                                                                        \
-    if (win_mask != nullptr)                                                                  \
-      hipLaunchKernelGGL((gate_bwd_dst_kernel<FPL, true>), dim3(att_grid(n_rows)),            \
-                         dim3(kAttThreads), 0, s, k);                                         \
-    else                                                                                      \
-      hipLaunchKernelGGL((gate_bwd_dst_kernel<FPL, false>), dim3(att_grid(n_rows)),           \
-                         dim3(kAttThreads), 0, s, k);                                         \
-  } while (0)
+  MGCN_REQUIRE(rowptr_t && dY && dHx, "%s: null array", fn);
+  MGCN_REQUIRE(nnz == 0 || (col_t && slot_map && g), "%s: null col / slot_map / g", fn);
+  MGCN_REQUIRE(da == nullptr || nnz == 0 || dl, "%s: da needs dl", fn);
+  MGCN_REQUIRE((da == nullptr && dc == nullptr) || w_sd, "%s: the rank-one terms need w_sd", fn);
+  MGCN_REQUIRE(lddy >= C && lddh >= C, "%s: leading dimension too small", fn);
+  MGCN_REQUIRE(s.order == nullptr || nnz == 0 || s.coef,
+               "%s: a schedule needs the coef scratch [nnz]", fn);
+  const bool sched = s.order != nullptr;
+  if (!sched) s = GateSched{};
+  GateBwdSrcArgs k{n_rows, C, rowptr_t, col_t, slot_map, dY, lddy, w_t, row_scale, g, dl,
+                   win_mask, w_sd, dc, da, dHx, lddh, s};
+  hipStream_t st = as_stream(stream);
+  if (s.n_heavy > 0)
+    if (int rc = gate_bwd_src_heavy(k, st)) return rc;
+  const int64_t n_work = n_rows - s.n_heavy;
+  if (n_work == 0) return MGCN_OK;
+  const bool is_max = win_mask != nullptr;
+#define CALL(FPL) GATE_LAUNCH(gate_bwd_src_kernel, FPL, is_max, sched, n_work, st, k)
   ATT_DISPATCH(C, CALL);
 #undef CALL
-  return check_launch("gate_bwd_dst_kernel");
+  return check_launch("gate_bwd_src_kernel");
 }
 
 extern "C" int mgcn_gate_bwd_src(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr_t,
@@ -386,28 +444,20 @@ extern "C" int mgcn_gate_bwd_src(int64_t n_rows, int64_t nnz, int32_t C, const i
                                  const float *g, const float *dl, const uint32_t *win_mask,
                                  const float *w_sd, const float *dc, float *da, float *dHx,
                                  int64_t lddh, void *stream) {
-  clear_error();
-  GATE_REQUIRE_SHAPE("mgcn_gate_bwd_src", n_rows, nnz, C);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr_t && dY && dHx, "mgcn_gate_bwd_src: null array");
-  MGCN_REQUIRE(nnz == 0 || (col_t && slot_map && g), "mgcn_gate_bwd_src: null col / slot_map / g");
-  MGCN_REQUIRE(da == nullptr || nnz == 0 || dl, "mgcn_gate_bwd_src: da needs dl");
-  MGCN_REQUIRE((da == nullptr && dc == nullptr) || w_sd,
-               "mgcn_gate_bwd_src: the rank-one terms need w_sd");
-  MGCN_REQUIRE(lddy >= C && lddh >= C, "mgcn_gate_bwd_src: leading dimension too small");
-  GateBwdSrcArgs k{n_rows, C, rowptr_t, col_t, slot_map, dY, lddy, w_t, row_scale, g, dl,
-                   win_mask, w_sd, dc, da, dHx, lddh};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                             \
-  do {                                                                                        \
-    if (win_mask != nullptr)                                                                  \
-      hipLaunchKernelGGL((gate_bwd_src_kernel<FPL, true>), dim3(att_grid(n_rows)),            \
-                         dim3(kAttThreads), 0, s, k);                                         \
-    else                                                                                      \
-      hipLaunchKernelGGL((gate_bwd_src_kernel<FPL, false>), dim3(att_grid(n_rows)),           \
-                         dim3(kAttThreads), 0, s, k);                                         \
-  } while (0)
-  ATT_DISPATCH(C, CALL);
-#undef CALL
-  return check_launch("gate_bwd_src_kernel");
+  return gate_bwd_src_run("mgcn_gate_bwd_src", n_rows, nnz, C, rowptr_t, col_t, slot_map, dY,
+                          lddy, w_t, row_scale, g, dl, win_mask, w_sd, dc, da, dHx, lddh,
+                          GateSched{}, stream);
+}
+
+extern "C" int mgcn_gate_bwd_src_sched(int64_t n_rows, int64_t nnz, int32_t C,
+                                       const int64_t *rowptr_t, const int32_t *col_t,
+                                       const int32_t *slot_map, const float *dY, int64_t lddy,
+                                       const float *w_t, const float *row_scale, const float *g,
+                                       const float *dl, const uint32_t *win_mask,
+                                       const float *w_sd, const float *dc, float *da, float *dHx,
+                                       int64_t lddh, const int32_t *order, int64_t n_heavy,
+                                       int64_t n_giant, float *coef, void *stream) {
+  return gate_bwd_src_run("mgcn_gate_bwd_src_sched", n_rows, nnz, C, rowptr_t, col_t, slot_map,
+                          dY, lddy, w_t, row_scale, g, dl, win_mask, w_sd, dc, da, dHx, lddh,
+                          GateSched{order, n_heavy, n_giant, coef}, stream);
 }

@@ -195,6 +195,15 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _vp, _vp]),
     "mgcn_gate_bwd_src": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # the three above + (order, n_heavy, n_giant[, coef scratch]) before the stream
+    "mgcn_gate_fwd_sched": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp,
+                                   _i64, _int, _vp, _int, _vp, _i64, _vp, _vp, _vp, _i64, _i64,
+                                   _vp, _vp]),
+    "mgcn_gate_bwd_dst_sched": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "mgcn_gate_bwd_src_sched": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp,
+                                       _vp]),
     "mgcn_multi_spmm_fwd": (_int, [_i64, _i32, _i32, MultiViewsC, _vp, _i64, _vp, _i64, _int, _int,
                                    _int, _vp]),
     "mgcn_multi_spmm_bwd": (_int, [_i64, _i32, _i32, MultiViewsC, _vp, _i64, _vp, _i64, _int, _int,

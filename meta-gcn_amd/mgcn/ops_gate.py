@@ -4,12 +4,38 @@ gradients are one ``gemm_tn``, the ReLU / bias / mean adjoint is
 ``relu_bwd_colsum``); :mod:`mgcn.ops` re-exports every name."""
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import _lib as L
 from ._call import _contig_f32, launch
 from .graph import GraphPlan, NormPlan
 from .ops_gemm import gemm_tn, relu_bwd_colsum
+
+
+# heavy rows (degree > 128, graph.schedule_rows) of a gated layer by workgroups
+# (the mgcn_gate_*_sched entries, bit-identical to the wave-per-row launches);
+# MGCN_GATE_HEAVY=0 keeps the wave-per-row launches for every row
+_GATE_HEAVY = os.environ.get("MGCN_GATE_HEAVY", "1") != "0"
+
+
+def set_gate_heavy_rows(enabled: bool) -> None:
+    """Send (True, the default) the heavy rows of a gated layer's three
+    launches through the workgroup path (mgcn_gate_fwd_sched / _bwd_dst_sched /
+    _bwd_src_sched) or keep (False; env MGCN_GATE_HEAVY=0) one wave per row
+    for every row.  Results are bitwise the same either way."""
+    global _GATE_HEAVY
+    _GATE_HEAVY = bool(enabled)
+
+
+def gate_heavy_rows() -> bool:
+    """The switch :func:`set_gate_heavy_rows` sets."""
+    return _GATE_HEAVY
+
+
+def _heavy(view) -> bool:
+    return _GATE_HEAVY and view.order is not None and view.n_heavy > 0
 
 
 def _max_mask(plan: GraphPlan, argmax: torch.Tensor) -> torch.Tensor:
@@ -36,6 +62,9 @@ class _GateAggregate(torch.autograd.Function):
     Saved: Hx, the gate (fwd slot order), the gate vectors, Y under ReLU, the
     winner bits under max.  Backward: relu_bwd_colsum, mgcn_gate_bwd_dst,
     mgcn_gate_bwd_src, and [da | dc]^T Hx as one mgcn_gemm_tn.
+
+    A view with heavy rows sends its launches through the ``_sched`` entries
+    (:func:`set_gate_heavy_rows`; timer names ``gate_*_heavy``): same bits.
 
     ``t`` is [E] in COO order or one element; ``w_fwd`` is ``norm.w_fwd`` as an
     autograd input when the norm carries history (else None).  Returns
@@ -72,10 +101,16 @@ class _GateAggregate(torch.autograd.Function):
         g = torch.empty(nnz, dtype=torch.float32, device=dev)
         is_max = reduce == L.REDUCE_MAX
         argmax = torch.empty(N, C, dtype=torch.int32, device=dev) if is_max else None
-        launch("gate_fwd", "mgcn_gate_fwd", dev, N, fwd.edges, lib.mgcn_gate_fwd,
-               N, nnz, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(fwd.eid), L.ptr(a), L.ptr(c),
-               L.ptr(ts), int(t_bcast), L.ptr(w), L.ptr(Hx), Hx.stride(0), reduce, L.ptr(b),
-               int(bool(relu)), L.ptr(Y), C, L.ptr(g), L.ptr(argmax), st)
+        args = (N, nnz, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(fwd.eid), L.ptr(a), L.ptr(c),
+                L.ptr(ts), int(t_bcast), L.ptr(w), L.ptr(Hx), Hx.stride(0), reduce, L.ptr(b),
+                int(bool(relu)), L.ptr(Y), C, L.ptr(g), L.ptr(argmax))
+        if _heavy(fwd):
+            coef = torch.empty(nnz, dtype=torch.float32, device=dev)
+            launch("gate_fwd_heavy", "mgcn_gate_fwd_sched", dev, N, fwd.edges,
+                   lib.mgcn_gate_fwd_sched, *args, L.ptr(fwd.order), fwd.n_heavy, fwd.n_giant,
+                   L.ptr(coef), st)
+        else:
+            launch("gate_fwd", "mgcn_gate_fwd", dev, N, fwd.edges, lib.mgcn_gate_fwd, *args, st)
         mask = _max_mask(plan, argmax) if is_max else None
         g_coo = torch.empty_like(g)
         if nnz:
@@ -117,15 +152,28 @@ class _GateAggregate(torch.autograd.Function):
         da = torch.empty(N, dtype=torch.float32, device=dev) if proj else None
         dw = torch.empty(nnz, dtype=torch.float32, device=dev) if need_w else None
         dHx = torch.empty(N, C, dtype=torch.float32, device=dev)
-        launch("gate_bwd_dst", "mgcn_gate_bwd_dst", dev, N, fwd.edges, lib.mgcn_gate_bwd_dst,
-               N, nnz, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hx), Hx.stride(0), L.ptr(dY),
-               dY.stride(0), L.ptr(w), L.ptr(g), L.ptr(mask), L.ptr(dg_in), L.ptr(dl), L.ptr(dc),
-               L.ptr(dw), st)
+        args = (N, nnz, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hx), Hx.stride(0), L.ptr(dY),
+                dY.stride(0), L.ptr(w), L.ptr(g), L.ptr(mask), L.ptr(dg_in), L.ptr(dl), L.ptr(dc),
+                L.ptr(dw))
+        if _heavy(fwd):
+            launch("gate_bwd_dst_heavy", "mgcn_gate_bwd_dst_sched", dev, N, fwd.edges,
+                   lib.mgcn_gate_bwd_dst_sched, *args, L.ptr(fwd.order), fwd.n_heavy,
+                   fwd.n_giant, st)
+        else:
+            launch("gate_bwd_dst", "mgcn_gate_bwd_dst", dev, N, fwd.edges,
+                   lib.mgcn_gate_bwd_dst, *args, st)
         slot = plan.slot_map() if nnz else None
-        launch("gate_bwd_src", "mgcn_gate_bwd_src", dev, N, bwd.edges, lib.mgcn_gate_bwd_src,
-               N, nnz, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
-               dY.stride(0), L.ptr(norm.w_bwd), L.ptr(norm.row_scale_bwd), L.ptr(g), L.ptr(dl),
-               L.ptr(mask), L.ptr(wsd), L.ptr(dc), L.ptr(da), L.ptr(dHx), C, st)
+        args = (N, nnz, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
+                dY.stride(0), L.ptr(norm.w_bwd), L.ptr(norm.row_scale_bwd), L.ptr(g), L.ptr(dl),
+                L.ptr(mask), L.ptr(wsd), L.ptr(dc), L.ptr(da), L.ptr(dHx), C)
+        if _heavy(bwd):
+            coef = torch.empty(nnz, dtype=torch.float32, device=dev)
+            launch("gate_bwd_src_heavy", "mgcn_gate_bwd_src_sched", dev, N, bwd.edges,
+                   lib.mgcn_gate_bwd_src_sched, *args, L.ptr(bwd.order), bwd.n_heavy,
+                   bwd.n_giant, L.ptr(coef), st)
+        else:
+            launch("gate_bwd_src", "mgcn_gate_bwd_src", dev, N, bwd.edges,
+                   lib.mgcn_gate_bwd_src, *args, st)
         dwsd = None
         if proj and ctx.needs_input_grad[1]:
             dwsd = gemm_tn(torch.stack([da, dc], dim=1), Hx).reshape(-1)  # [w_src | w_dst]
