@@ -755,7 +755,8 @@ size_t mgcn_residual_layer_bwd_workspace_bytes(int64_t n_rows, int32_t F);
  *   dX = dH W^T + dS Wr
  *   colsums[0:F] = sum_i dA (undivided: the bias gradient), [F:2F] = sum_i dS
  * [dW | dWr^T] = X^T DH is then one mgcn_gemm_tn_split.  dH is bit for bit
- * mgcn_spmm_bwd's of dA.
+ * mgcn_spmm_bwd's of dA.  masks is read as 8-byte pairs: 8-byte aligned, like
+ * the forward's (else MGCN_EINVAL).
  */
 int mgcn_residual_layer_bwd(int64_t n_rows, int32_t F, const int64_t *rowptr_t,
                             const int32_t *col_t, const int32_t *eid_t, const float *w_t,
@@ -774,7 +775,9 @@ int mgcn_residual_layer_bwd(int64_t n_rows, int32_t F, const int64_t *rowptr_t,
  * may be NULL).  The backward runs the layers top-down: dZ the top layer's
  * upstream gradient, dW[l] ([F][F]) and dWr[l] ([F][F], the Linear layout)
  * written per layer, sums + 2 F l = (bias | rbias gradient) of layer l, dX0
- * (nullable) the gradient of X0.  Bitwise the layer-by-layer calls.
+ * (nullable) the gradient of X0.  Bitwise the layer-by-layer calls.  Both
+ * check (order, n_heavy, n_giant), the 8-byte alignment of masks and the
+ * 16-byte alignment of X0 / dZ / dX0 rows before any launch (MGCN_EINVAL).
  */
 int mgcn_residual_stack_fwd(int64_t n_rows, int32_t F, int32_t n_layers, const int64_t *rowptr,
                             const int32_t *col, const int32_t *eid, const float *w,

@@ -715,6 +715,7 @@ extern "C" int mgcn_residual_layer_bwd(int64_t n_rows, int32_t F, const int64_t 
   MGCN_REQUIRE(al16(dZ, lddz) && al16(dX, lddx) && al16(DH, lddh) && lddz >= F && lddx >= F &&
                    lddh >= 2 * F && ldw >= F && ldwr >= F,
                "mgcn_residual_layer_bwd: dZ / dX / DH need 16-byte aligned rows (DH: 2F wide)");
+  MGCN_REQUIRE((uintptr_t)masks % 8 == 0, "mgcn_residual_layer_bwd: masks not 8-byte aligned");
   MGCN_REQUIRE(order == nullptr || (0 <= n_giant && n_giant <= n_heavy && n_heavy <= n_rows),
                "mgcn_residual_layer_bwd: need 0 <= n_giant <= n_heavy <= n_rows");
   const size_t need = mgcn_residual_layer_bwd_workspace_bytes(n_rows, F);
@@ -831,6 +832,10 @@ extern "C" int mgcn_residual_stack_bwd(int64_t n_rows, int32_t F, int32_t n_laye
   }
   MGCN_REQUIRE(F == kRF && al16(dZ, lddz) && lddz >= F && al16(X0, ldx) && ldx >= F,
                "mgcn_residual_stack_bwd: F must be 32, dZ / X0 16-byte aligned rows");
+  MGCN_REQUIRE((uintptr_t)masks % 8 == 0 && al16(dX0, F),
+               "mgcn_residual_stack_bwd: masks not 8-byte / dX0 not 16-byte aligned");
+  MGCN_REQUIRE(order == nullptr || (0 <= n_giant && n_giant <= n_heavy && n_heavy <= n_rows),
+               "mgcn_residual_stack_bwd: need 0 <= n_giant <= n_heavy <= n_rows");
   // the top layer's mask pass reads dZ; every lower layer's runs fused in the
   // store of the layer above's dX (its dS / dA / column sums straight from there)
   const int32_t top = n_layers - 1;

@@ -19,6 +19,7 @@ from conftest import load_golden
 from multi_kernel_ref import (DEGREES, FIXTURES, ISOLATED, MODEL_ARGS, MODEL_FIXTURE, check,
                               degree_graphs, fixture_inputs, fixture_tensors, make_module,
                               random_graph, ref_run, zero_graph)
+from residual_ref import BAND, SENT, Guarded  # noqa: F401  (the sentinel-guarded buffer)
 
 pytestmark = pytest.mark.gpu
 
@@ -356,22 +357,7 @@ def test_entries_reject_bad_arguments(cuda):
 
 
 # --------------------------------------------------------------- guard bands
-SENT = 0x7FBADBAD  # a NaN bit pattern no kernel writes
-BAND = 4096
-
-
-class Guarded:
-    """A [rows, cols] float32 tensor between two bands of sentinel words."""
-
-    def __init__(self, rows, cols, dev):
-        self.base = torch.full((BAND + rows * cols + BAND,), SENT, dtype=torch.int32, device=dev)
-        self.t = self.base[BAND:BAND + rows * cols].view(torch.float32).view(rows, cols)
-
-    def intact(self):
-        b = self.base
-        return bool((b[:BAND] == SENT).all()) and bool((b[b.numel() - BAND:] == SENT).all())
-
-
+# (Guarded, SENT, BAND: residual_ref.py, shared with test_gpu_residual_shapes.py)
 @pytest.mark.parametrize("n", [67, 300])
 @pytest.mark.parametrize("C", [8, 30, 33, 128, 130])
 def test_guard_bands_stay_untouched(cuda, C, n):
