@@ -1269,6 +1269,94 @@ int mgcn_gate_bwd_src_sched(int64_t n_rows, int64_t nnz, int32_t C, const int64_
                             int64_t lddh, const int32_t *order, int64_t n_heavy,
                             int64_t n_giant, float *coef, void *stream);
 
+/*
+ * The six gate entries on bf16 feature rows.  Added under ABI 22 as the
+ * attention _bf16 siblings were, without changing any existing entry
+ * (backward-compatible: MGCN_ABI_VERSION stays 22).
+ *
+ * bf16 (bit patterns as uint16_t; leading dimensions counted in elements):
+ * Hx, Y, dY, dHx.  fp32 as in the entries above: a, c, t, w / w_t, row_scale,
+ * g, dl, dc, da, dw, dg_in, bias, w_sd and the coef scratch.  argmax, win_mask
+ * and slot_map are unchanged.
+ *
+ * Contract (that of mgcn_spmm_fwd_bf16 and of the attention siblings): a
+ * loaded bf16 element is widened to fp32 exactly; every value is then formed
+ * by the operations of the fp32 entry in the same order; each bf16 output
+ * element is rounded once, to nearest even, at its store.  So g, dl, dc, da,
+ * dw and argmax have the bits of the fp32 entry called on the upcast rows, and
+ * Y and dHx the bits of the fp32 entry's output rounded to bf16.  dHx includes
+ * the two rank-one terms da w_sd[0:C] + dc w_sd[C:2C]: they are added in fp32
+ * before the single rounding, in the kernel that forms the row (wave kernel
+ * and heavy-row workgroup alike).
+ *
+ * Arguments, their order, the nullable ones, the row-range use, the limits
+ * (1 <= C <= 1024, nnz < 2^31, any leading dimension >= C), MGCN_EINVAL before
+ * any launch, n_rows == 0 as a no-op, the absence of atomics and the fixed
+ * summation orders are those of the fp32 entries.  Rows need no alignment
+ * beyond the 2 bytes of an element (the wave kernels access single elements;
+ * the heavy-row workgroups pick 8-, 4- or 2-byte gathers from the alignment of
+ * the pointers and leading dimensions, per launch).
+ *
+ * Mean: the fp32 route divides the dY rows by their count once and hands the
+ * divided fp32 rows to both adjoint entries; a bf16 dY cannot carry the
+ * quotient without a second rounding.  The four adjoint entries therefore take
+ * one more argument after the fp32 entry's arrays, cnt (nullable; fp32, indexed
+ * by destination node, each >= 1; as mgcn_spmm_bwd_bf16 takes it): with cnt
+ * given every loaded dY element is widened and divided by its destination's
+ * count (IEEE division, round to nearest) before any other use --
+ * mgcn_gate_bwd_dst_bf16 by cnt[row] (the row-range caller advances cnt with
+ * dY), mgcn_gate_bwd_src_bf16 by cnt[col_k] of the gathered column -- so the
+ * value entering every later operation is bit for bit the fp32 route's.  cnt
+ * belongs to mean and win_mask to max: giving both is MGCN_EINVAL.
+ *
+ * The _sched_bf16 entries send order[0, n_heavy) through the workgroup path
+ * with bf16 rows and the remaining rows through the wave kernels, with the
+ * bits of the _bf16 entries without a schedule; coef stays fp32 [nnz].
+ */
+int mgcn_gate_fwd_bf16(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
+                       const int32_t *col, const int32_t *eid, const float *a, const float *c,
+                       const float *t, int t_bcast, const float *w, const uint16_t *Hx,
+                       int64_t ldh, int reduce, const float *bias, int relu, uint16_t *Y,
+                       int64_t ldy, float *g, int32_t *argmax, void *stream);
+
+int mgcn_gate_bwd_dst_bf16(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
+                           const int32_t *col, const uint16_t *Hx, int64_t ldh,
+                           const uint16_t *dY, int64_t lddy, const float *w, const float *g,
+                           const uint32_t *win_mask, const float *dg_in, float *dl, float *dc,
+                           float *dw, const float *cnt, void *stream);
+
+int mgcn_gate_bwd_src_bf16(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr_t,
+                           const int32_t *col_t, const int32_t *slot_map, const uint16_t *dY,
+                           int64_t lddy, const float *w_t, const float *row_scale,
+                           const float *g, const float *dl, const uint32_t *win_mask,
+                           const float *w_sd, const float *dc, float *da, uint16_t *dHx,
+                           int64_t lddh, const float *cnt, void *stream);
+
+int mgcn_gate_fwd_sched_bf16(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
+                             const int32_t *col, const int32_t *eid, const float *a,
+                             const float *c, const float *t, int t_bcast, const float *w,
+                             const uint16_t *Hx, int64_t ldh, int reduce, const float *bias,
+                             int relu, uint16_t *Y, int64_t ldy, float *g, int32_t *argmax,
+                             const int32_t *order, int64_t n_heavy, int64_t n_giant, float *coef,
+                             void *stream);
+
+int mgcn_gate_bwd_dst_sched_bf16(int64_t n_rows, int64_t nnz, int32_t C, const int64_t *rowptr,
+                                 const int32_t *col, const uint16_t *Hx, int64_t ldh,
+                                 const uint16_t *dY, int64_t lddy, const float *w,
+                                 const float *g, const uint32_t *win_mask, const float *dg_in,
+                                 float *dl, float *dc, float *dw, const float *cnt,
+                                 const int32_t *order, int64_t n_heavy, int64_t n_giant,
+                                 void *stream);
+
+int mgcn_gate_bwd_src_sched_bf16(int64_t n_rows, int64_t nnz, int32_t C,
+                                 const int64_t *rowptr_t, const int32_t *col_t,
+                                 const int32_t *slot_map, const uint16_t *dY, int64_t lddy,
+                                 const float *w_t, const float *row_scale, const float *g,
+                                 const float *dl, const uint32_t *win_mask, const float *w_sd,
+                                 const float *dc, float *da, uint16_t *dHx, int64_t lddh,
+                                 const float *cnt, const int32_t *order, int64_t n_heavy,
+                                 int64_t n_giant, float *coef, void *stream);
+
 /* --------------------------------------------------- multi-kernel layers */
 
 /*

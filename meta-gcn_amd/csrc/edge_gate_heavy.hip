@@ -29,6 +29,16 @@
 // wrote.
 //
 // Barriers only: no atomics, no hand-off between workgroups.
+//
+// bf16 rows (the mgcn_gate_*_sched_bf16 entries; argument structs with Row =
+// uint16_t): the heavy-row body gathers and stores through load_x / store_y
+// with T = uint16_t -- its LDS holds fp32 products and metadata words with
+// either T, so heavy_shape is unchanged -- and the chunk kernel through
+// row_ld.  A bf16 dHx element must be rounded once, so the by-source kernel
+// cannot add the rank-one terms to a stored row: wave 0 sums da before the
+// body and the terms are the body's last fp32 step (GateSrcEpi).  Mean: the
+// body's BWD_MEAN divides each gathered dY element by cnt[col] before its
+// product, the chunk kernel divides its dY row by cnt[row].
 
 #include <atomic>
 
@@ -46,9 +56,9 @@ template <int HB>
 constexpr int kQuads = HB >= 1024 ? 1 : 0;
 
 // ----------------------------------------------------------------- forward
-template <int VEC, int MODE, int HB>
-__global__ __launch_bounds__(HB) void gate_fwd_heavy_kernel(const SpmmArgs s, const GateFwdArgs a,
-                                                            int FC, int BE) {
+template <int VEC, int MODE, int HB, class A = GateFwdArgs>
+__global__ __launch_bounds__(HB) void gate_fwd_heavy_kernel(const SpmmArgs s, const A a, int FC,
+                                                            int BE) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int64_t row = s.heavy_rows[blockIdx.x];
   const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
@@ -63,14 +73,14 @@ __global__ __launch_bounds__(HB) void gate_fwd_heavy_kernel(const SpmmArgs s, co
     a.s.coef[k] = a.w != nullptr ? __fmul_rn(g, a.w[k]) : g;
   }
   __syncthreads();  // the row's coef: written above, read below as s.w
-  heavy_row_block<VEC, MODE, HB, kQuads<HB>>(s, FC, BE, blockIdx.x, smem);
+  heavy_row_block<VEC, MODE, HB, kQuads<HB>, typename A::Row>(s, FC, BE, blockIdx.x, smem);
 }
 
 // ------------------------------------------------- adjoint, by destination
 // Chunk c of heavy row order[blockIdx.x] by wave c (grid-stride over the
 // row's chunks along blockIdx.y): gate_bwd_dst_kernel's chunk body.
-template <int FPL, bool MAX>
-__global__ __launch_bounds__(kAttThreads) void gate_bwd_dst_chunk_kernel(GateBwdDstArgs a,
+template <int FPL, bool MAX, class A = GateBwdDstArgs>
+__global__ __launch_bounds__(kAttThreads) void gate_bwd_dst_chunk_kernel(A a,
                                                                          const int32_t *rows) {
   constexpr int U = gather_unroll<FPL>();
   const int lane = threadIdx.x & 63;
@@ -85,7 +95,14 @@ __global__ __launch_bounds__(kAttThreads) void gate_bwd_dst_chunk_kernel(GateBwd
 #pragma unroll
   for (int i = 0; i < FPL; ++i) {
     const int f = lane + 64 * i;
-    dy[i] = f < C ? a.dY[row * a.lddy + f] : 0.0f;
+    dy[i] = row_ld(f < C, a.dY, row * a.lddy + f);
+  }
+  if constexpr (A::kCnt) {  // mean over bf16 rows: the fp32 path's divided row
+    if (a.cnt != nullptr) {
+      const float cn = a.cnt[row];
+#pragma unroll
+      for (int i = 0; i < FPL; ++i) dy[i] = __fdiv_rn(dy[i], cn);
+    }
   }
   for (int64_t ch = wave0; ch < n_chunks; ch += nwaves) {
     const int64_t k0 = beg + 64 * ch;
@@ -102,7 +119,7 @@ __global__ __launch_bounds__(kAttThreads) void gate_bwd_dst_chunk_kernel(GateBwd
           const int f = lane + 64 * i;
           bool ld = on && f < C;
           if constexpr (MAX) ld = ld && won(a.win, k0 + kk + u, W, f);
-          hp[u][i] = ld ? a.Hx[c * a.ldh + f] : 0.0f;
+          hp[u][i] = row_ld(ld, a.Hx, c * a.ldh + f);
         }
       }
 #pragma unroll
@@ -130,7 +147,8 @@ __global__ __launch_bounds__(kAttThreads) void gate_bwd_dst_chunk_kernel(GateBwd
 // dc of the heavy rows, one wave per row: the wave kernel's sum of the row's
 // dl (lane u adds dl[k0 + u] chunk after chunk, then the butterfly), re-read
 // from memory.
-__global__ __launch_bounds__(kAttThreads) void gate_dc_heavy_kernel(GateBwdDstArgs a) {
+template <class A = GateBwdDstArgs>
+__global__ __launch_bounds__(kAttThreads) void gate_dc_heavy_kernel(A a) {
   const int lane = threadIdx.x & 63;
   const int64_t i = blockIdx.x * (int64_t)kAttWaves + (threadIdx.x >> 6);
   if (i >= a.s.n_heavy) return;
@@ -146,10 +164,25 @@ __global__ __launch_bounds__(kAttThreads) void gate_dc_heavy_kernel(GateBwdDstAr
 }
 
 // ------------------------------------------------------ adjoint, by source
-template <int VEC, int MODE, int HB>
-__global__ __launch_bounds__(HB) void gate_bwd_src_heavy_kernel(const SpmmArgs s,
-                                                                const GateBwdSrcArgs a, int FC,
-                                                                int BE) {
+// the rank-one terms of dHx[row, f] as the heavy-row body's last fp32 step
+// (bf16 rows): the wave kernel's two adds, in its order
+struct GateSrcEpi {
+  const float *wsd;
+  int C;
+  float dav, dcv;
+  bool has_da, has_dc;
+  __device__ __forceinline__ float operator()(int f, float v) const {
+    if (wsd != nullptr) {
+      if (has_da) v = __fadd_rn(v, __fmul_rn(dav, wsd[f]));
+      if (has_dc) v = __fadd_rn(v, __fmul_rn(dcv, wsd[C + f]));
+    }
+    return v;
+  }
+};
+
+template <int VEC, int MODE, int HB, class A = GateBwdSrcArgs>
+__global__ __launch_bounds__(HB) void gate_bwd_src_heavy_kernel(const SpmmArgs s, const A a,
+                                                                int FC, int BE) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int t = threadIdx.x;
   const int64_t row = s.heavy_rows[blockIdx.x];
@@ -158,14 +191,13 @@ __global__ __launch_bounds__(HB) void gate_bwd_src_heavy_kernel(const SpmmArgs s
     const float g = a.g[a.slot[k]];
     a.s.coef[k] = a.w_t != nullptr ? __fmul_rn(g, a.w_t[k]) : g;
   }
-  __syncthreads();  // the row's coef: written above, read below as s.w
-  // dHx[row, f] = chain [* row_scale]; ends on a barrier
-  heavy_row_block<VEC, MODE, HB, kQuads<HB>>(s, FC, BE, blockIdx.x, smem);
-  if (a.da == nullptr && a.dc == nullptr) return;
-  float dav = 0.0f;
-  if (a.da != nullptr) {
-    if (t < 64) {
-      float part = 0.0f;  // lane t's share of sum_row dl, in the wave kernel's order
+  if constexpr (sizeof(typename A::Row) != sizeof(float)) {
+    // bf16 rows: da first (wave 0, the wave kernel's order), handed to every
+    // thread through smem[0] -- read before the body's first barrier, written
+    // by the body only after it -- then the body rounds chain [* row_scale]
+    // + da w_sd[f] + dc w_sd[C + f] once at its store
+    if (a.da != nullptr && t < 64) {
+      float part = 0.0f;
       for (int64_t k0 = beg; k0 < end; k0 += 64) {
         const int64_t k = k0 + t;
         if (k < end) part = __fadd_rn(part, a.dl[a.slot[k]]);
@@ -176,31 +208,56 @@ __global__ __launch_bounds__(HB) void gate_bwd_src_heavy_kernel(const SpmmArgs s
         smem[0] = tot;
       }
     }
-    __syncthreads();
-    dav = smem[0];
-  }
-  const float dcv = a.dc != nullptr ? a.dc[row] : 0.0f;
-  const int C = a.C;
-  // thread t < fc stored feature f0 + t of every chunk (heavy_row_block)
-  for (int f0 = 0; f0 < C; f0 += FC) {
-    const int fc = C - f0 < FC ? C - f0 : FC;
-    if (t < fc) {
-      const int f = f0 + t;
-      float v = a.dHx[row * a.lddh + f];
-      if (a.da != nullptr) v = __fadd_rn(v, __fmul_rn(dav, a.wsd[f]));
-      if (a.dc != nullptr) v = __fadd_rn(v, __fmul_rn(dcv, a.wsd[C + f]));
-      a.dHx[row * a.lddh + f] = v;
+    __syncthreads();  // the row's coef and da
+    const GateSrcEpi epi{a.wsd, a.C, a.da != nullptr ? smem[0] : 0.0f,
+                         a.dc != nullptr ? a.dc[row] : 0.0f, a.da != nullptr, a.dc != nullptr};
+    heavy_row_block<VEC, MODE, HB, kQuads<HB>, typename A::Row>(s, FC, BE, blockIdx.x, smem, epi);
+  } else {
+    __syncthreads();  // the row's coef: written above, read below as s.w
+    // dHx[row, f] = chain [* row_scale]; ends on a barrier
+    heavy_row_block<VEC, MODE, HB, kQuads<HB>>(s, FC, BE, blockIdx.x, smem);
+    if (a.da == nullptr && a.dc == nullptr) return;
+    float dav = 0.0f;
+    if (a.da != nullptr) {
+      if (t < 64) {
+        float part = 0.0f;  // lane t's share of sum_row dl, in the wave kernel's order
+        for (int64_t k0 = beg; k0 < end; k0 += 64) {
+          const int64_t k = k0 + t;
+          if (k < end) part = __fadd_rn(part, a.dl[a.slot[k]]);
+        }
+        const float tot = wave_sum(part);
+        if (t == 0) {
+          a.da[row] = tot;
+          smem[0] = tot;
+        }
+      }
+      __syncthreads();
+      dav = smem[0];
+    }
+    const float dcv = a.dc != nullptr ? a.dc[row] : 0.0f;
+    const int C = a.C;
+    // thread t < fc stored feature f0 + t of every chunk (heavy_row_block)
+    for (int f0 = 0; f0 < C; f0 += FC) {
+      const int fc = C - f0 < FC ? C - f0 : FC;
+      if (t < fc) {
+        const int f = f0 + t;
+        float v = a.dHx[row * a.lddh + f];
+        if (a.da != nullptr) v = __fadd_rn(v, __fmul_rn(dav, a.wsd[f]));
+        if (a.dc != nullptr) v = __fadd_rn(v, __fmul_rn(dcv, a.wsd[C + f]));
+        a.dHx[row * a.lddh + f] = v;
+      }
     }
   }
 }
 
 // ------------------------------------------------------------------- host
 // widest vector the gathered and the written rows both allow (spmm.hip)
-int gate_vec(int32_t F, const void *p0, int64_t ld0, const void *p1, int64_t ld1) {
+// (esz: bytes per row element -- 4, or 2 for bf16 rows)
+int gate_vec(int32_t F, const void *p0, int64_t ld0, const void *p1, int64_t ld1, int esz) {
   auto ok = [&](int v) {
     return F % v == 0 && ld0 % v == 0 && ld1 % v == 0 &&
-           reinterpret_cast<uintptr_t>(p0) % (4 * v) == 0 &&
-           reinterpret_cast<uintptr_t>(p1) % (4 * v) == 0;
+           reinterpret_cast<uintptr_t>(p0) % (esz * v) == 0 &&
+           reinterpret_cast<uintptr_t>(p1) % (esz * v) == 0;
   };
   return ok(4) ? 4 : ok(2) ? 2 : 1;
 }
@@ -245,18 +302,19 @@ int launch_rows(SpmmArgs s, const A &a, const int32_t *rows, int64_t n, int lds_
   const HeavyShape h = heavy_shape(s.F, VEC, HB, lds_budget);
   static std::atomic<uint64_t> attr_set{0};
   if constexpr (MODE == FWD_SUM || MODE == FWD_MAX) {
-    if (int rc = allow_lds(reinterpret_cast<const void *>(&gate_fwd_heavy_kernel<VEC, MODE, HB>),
-                           attr_set))
+    if (int rc = allow_lds(
+            reinterpret_cast<const void *>(&gate_fwd_heavy_kernel<VEC, MODE, HB, A>), attr_set))
       return rc;
-    hipLaunchKernelGGL((gate_fwd_heavy_kernel<VEC, MODE, HB>), dim3((unsigned)n), dim3(HB), h.lds,
-                       stream, s, a, h.FC, h.BE);
+    hipLaunchKernelGGL((gate_fwd_heavy_kernel<VEC, MODE, HB, A>), dim3((unsigned)n), dim3(HB),
+                       h.lds, stream, s, a, h.FC, h.BE);
     return check_launch("gate_fwd_heavy_kernel");
   } else {
     if (int rc = allow_lds(
-            reinterpret_cast<const void *>(&gate_bwd_src_heavy_kernel<VEC, MODE, HB>), attr_set))
+            reinterpret_cast<const void *>(&gate_bwd_src_heavy_kernel<VEC, MODE, HB, A>),
+            attr_set))
       return rc;
-    hipLaunchKernelGGL((gate_bwd_src_heavy_kernel<VEC, MODE, HB>), dim3((unsigned)n), dim3(HB),
-                       h.lds, stream, s, a, h.FC, h.BE);
+    hipLaunchKernelGGL((gate_bwd_src_heavy_kernel<VEC, MODE, HB, A>), dim3((unsigned)n),
+                       dim3(HB), h.lds, stream, s, a, h.FC, h.BE);
     return check_launch("gate_bwd_src_heavy_kernel");
   }
 }
@@ -275,15 +333,25 @@ int launch_heavy(const SpmmArgs &s, const A &a, hipStream_t stream) {
 
 template <int MODE, class A>
 int launch_heavy_v(const SpmmArgs &s, const A &a, hipStream_t stream) {
-  const int vec = gate_vec(s.F, s.X, s.ldx, s.Y, s.ldy);
+  const int vec = gate_vec(s.F, s.X, s.ldx, s.Y, s.ldy, (int)sizeof(typename A::Row));
   if (vec == 4) return launch_heavy<4, MODE>(s, a, stream);
   if (vec == 2) return launch_heavy<2, MODE>(s, a, stream);
   return launch_heavy<1, MODE>(s, a, stream);
 }
 
-}  // namespace
+// (the SpMM block holds X and Y as float pointers; bf16 rows travel behind
+// them and the body casts back to its T)
+template <class R>
+const float *as_f(const R *p) {
+  return reinterpret_cast<const float *>(p);
+}
+template <class R>
+float *as_f(R *p) {
+  return reinterpret_cast<float *>(p);
+}
 
-int gate_fwd_heavy(const GateFwdArgs &a, hipStream_t stream) {
+template <class A>
+int fwd_heavy(const A &a, hipStream_t stream) {
   SpmmArgs s{};
   s.n_rows = a.n_rows;
   s.F = a.C;
@@ -292,9 +360,9 @@ int gate_fwd_heavy(const GateFwdArgs &a, hipStream_t stream) {
   s.col = a.col;
   s.eid = a.eid;
   s.w = a.s.coef;
-  s.X = a.Hx;
+  s.X = as_f(a.Hx);
   s.ldx = a.ldh;
-  s.Y = a.Y;
+  s.Y = as_f(a.Y);
   s.ldy = a.ldy;
   s.bias = a.bias;
   s.argmax_out = a.argmax;
@@ -304,7 +372,8 @@ int gate_fwd_heavy(const GateFwdArgs &a, hipStream_t stream) {
   return launch_heavy_v<FWD_SUM>(s, a, stream);
 }
 
-int gate_bwd_dst_heavy(const GateBwdDstArgs &a, hipStream_t stream) {
+template <class A>
+int bwd_dst_heavy(const A &a, hipStream_t stream) {
   // waves along y per row: a giant row's chunks one or two per wave, the
   // other heavy rows' (129 .. giant_thr slots) a few
   auto chunks = [&](const int32_t *rows, int64_t n, unsigned blocks_y) {
@@ -313,11 +382,11 @@ int gate_bwd_dst_heavy(const GateBwdDstArgs &a, hipStream_t stream) {
 #define CALL(FPL)                                                                             \
   do {                                                                                        \
     if (a.win != nullptr)                                                                     \
-      hipLaunchKernelGGL((gate_bwd_dst_chunk_kernel<FPL, true>), grid, block, 0, stream, a,   \
-                         rows);                                                               \
+      hipLaunchKernelGGL((gate_bwd_dst_chunk_kernel<FPL, true, A>), grid, block, 0, stream,   \
+                         a, rows);                                                            \
     else                                                                                      \
-      hipLaunchKernelGGL((gate_bwd_dst_chunk_kernel<FPL, false>), grid, block, 0, stream, a,  \
-                         rows);                                                               \
+      hipLaunchKernelGGL((gate_bwd_dst_chunk_kernel<FPL, false, A>), grid, block, 0, stream,  \
+                         a, rows);                                                            \
   } while (0)
     ATT_DISPATCH(a.C, CALL);
 #undef CALL
@@ -327,11 +396,12 @@ int gate_bwd_dst_heavy(const GateBwdDstArgs &a, hipStream_t stream) {
   if (int rc = check_launch("gate_bwd_dst_chunk_kernel")) return rc;
   if (a.dc == nullptr) return MGCN_OK;
   const unsigned blocks = (unsigned)((a.s.n_heavy + kAttWaves - 1) / kAttWaves);
-  hipLaunchKernelGGL(gate_dc_heavy_kernel, dim3(blocks), dim3(kAttThreads), 0, stream, a);
+  hipLaunchKernelGGL(gate_dc_heavy_kernel<A>, dim3(blocks), dim3(kAttThreads), 0, stream, a);
   return check_launch("gate_dc_heavy_kernel");
 }
 
-int gate_bwd_src_heavy(const GateBwdSrcArgs &a, hipStream_t stream) {
+template <class A>
+int bwd_src_heavy(const A &a, hipStream_t stream) {
   SpmmArgs s{};
   s.n_rows = a.n_rows;
   s.F = a.C;
@@ -339,15 +409,38 @@ int gate_bwd_src_heavy(const GateBwdSrcArgs &a, hipStream_t stream) {
   s.rowptr = a.rowptr;
   s.col = a.col;
   s.w = a.s.coef;
-  s.X = a.dY;
+  s.X = as_f(a.dY);
   s.ldx = a.lddy;
-  s.Y = a.dHx;
+  s.Y = as_f(a.dHx);
   s.ldy = a.lddh;
   s.row_scale = a.row_scale;
   s.win_mask = a.win;
   s.slot_map = a.slot;
   if (a.win != nullptr) return launch_heavy_v<BWD_MAXM>(s, a, stream);
+  if constexpr (A::kCnt) {
+    if (a.cnt != nullptr) {  // mean: every gathered element divided by cnt[col]
+      s.cnt = a.cnt;
+      return launch_heavy_v<BWD_MEAN>(s, a, stream);
+    }
+  }
   return launch_heavy_v<BWD_SUM>(s, a, stream);
+}
+
+}  // namespace
+
+int gate_fwd_heavy(const GateFwdArgs &a, hipStream_t stream) { return fwd_heavy(a, stream); }
+int gate_fwd_heavy(const GateFwdArgsBf16 &a, hipStream_t stream) { return fwd_heavy(a, stream); }
+int gate_bwd_dst_heavy(const GateBwdDstArgs &a, hipStream_t stream) {
+  return bwd_dst_heavy(a, stream);
+}
+int gate_bwd_dst_heavy(const GateBwdDstArgsBf16 &a, hipStream_t stream) {
+  return bwd_dst_heavy(a, stream);
+}
+int gate_bwd_src_heavy(const GateBwdSrcArgs &a, hipStream_t stream) {
+  return bwd_src_heavy(a, stream);
+}
+int gate_bwd_src_heavy(const GateBwdSrcArgsBf16 &a, hipStream_t stream) {
+  return bwd_src_heavy(a, stream);
 }
 
 }  // namespace mgcn

@@ -209,10 +209,15 @@ __device__ unsigned long long g_hprof[3][256][2];
 // kernel's extern array (config 3).
 // (Q: edge quads in flight per producer thread, 0 = the kernel's choice; a
 // caller with fewer registers to spare passes a smaller one; T: the storage
-// of a.X and a.Y -- float, or uint16_t for bf16 rows behind the same pointers)
-template <int VEC, int MODE, int HB, int Q = 0, typename T = float>
+// of a.X and a.Y -- float, or uint16_t for bf16 rows behind the same pointers;
+// epi(f, v): the adjoint modes' last fp32 step on element f of the row before
+// its one store -- the default leaves v as it is)
+struct HeavyNoEpi {
+  __device__ __forceinline__ float operator()(int, float v) const { return v; }
+};
+template <int VEC, int MODE, int HB, int Q = 0, typename T = float, class Epi = HeavyNoEpi>
 __device__ __forceinline__ void heavy_row_block(const SpmmArgs &a, int FC, int BE, int64_t hidx,
-                                                float *__restrict__ smem) {
+                                                float *__restrict__ smem, Epi epi = Epi{}) {
   constexpr bool kFwd = (MODE == FWD_SUM || MODE == FWD_MAX);
   constexpr bool kNeedEid = (MODE == FWD_MAX || MODE == BWD_MAX);
   constexpr bool kMaxBwd = (MODE == BWD_MAX || MODE == BWD_MAXM);
@@ -481,6 +486,7 @@ __device__ __forceinline__ void heavy_row_block(const SpmmArgs &a, int FC, int B
       } else {
         float v = acc;
         if (a.row_scale != nullptr) v = __fmul_rn(v, a.row_scale[row]);
+        v = epi(f, v);
         if (a.accumulate) v = __fadd_rn(load_y(dst), v);
         store_y(dst, v);
       }

@@ -204,6 +204,23 @@ SIGNATURES = {
     "mgcn_gate_bwd_src_sched": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp,
                                        _vp]),
+    # bf16 rows (Hx, Y, dY, dHx): the six above; the four adjoint entries take
+    # cnt (nullable, mean) after the fp32 entry's arrays
+    "mgcn_gate_fwd_bf16": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp,
+                                  _i64, _int, _vp, _int, _vp, _i64, _vp, _vp, _vp]),
+    "mgcn_gate_bwd_dst_bf16": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mgcn_gate_bwd_src_bf16": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mgcn_gate_fwd_sched_bf16": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp,
+                                        _vp, _i64, _int, _vp, _int, _vp, _i64, _vp, _vp, _vp,
+                                        _i64, _i64, _vp, _vp]),
+    "mgcn_gate_bwd_dst_sched_bf16": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                            _vp]),
+    "mgcn_gate_bwd_src_sched_bf16": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                            _i64, _i64, _vp, _vp]),
     "mgcn_multi_spmm_fwd": (_int, [_i64, _i32, _i32, MultiViewsC, _vp, _i64, _vp, _i64, _int, _int,
                                    _int, _vp]),
     "mgcn_multi_spmm_bwd": (_int, [_i64, _i32, _i32, MultiViewsC, _vp, _i64, _vp, _i64, _int, _int,

@@ -226,7 +226,8 @@ class NodeModelAdditive(NodeModelBase):
         ea = edge_attr.to(torch.float32)
         if g_coo is not None:
             ea = g_coo.unsqueeze(1) * ea
-        ye = linear(scatter_(self.aggr, ea, edge_index[1], y.size(0)), self.weight_edge)
+        ye = linear(scatter_(self.aggr, ea, edge_index[1], y.size(0)),
+                    self.weight_edge.to(torch.float32))  # (a bf16 module: cast through autograd)
         y = y + ye.to(y.dtype)
         if self.bias is not None:
             y = y + self.bias.to(y.dtype)
@@ -265,11 +266,14 @@ class EdgeGateProj(nn.Module):
     def gate_terms(self, edge_attr, num_edges):
         """(w_src, w_dst, t) of :func:`mgcn.ops.gate_aggregate`: t holds the
         edge-feature projection and the bias (one element without edge
-        features, so the kernel reads it from the device)."""
+        features, so the kernel reads it from the device).  The parameters
+        go as they are, fp32 or -- a module after ``.to(torch.bfloat16)`` --
+        bf16: gate_aggregate casts them to fp32 through autograd."""
         t = self.bias
         if edge_attr is not None:
             assert self.in_edgedim is not None  # gcn_base_models.py:364
-            t = linear_bias(edge_attr.to(torch.float32), self.linedge.weight, None).view(-1)
+            t = linear_bias(edge_attr.to(torch.float32), self.linedge.weight.to(torch.float32),
+                            None).view(-1)
             if self.bias is not None:
                 t = t + self.bias
         return self.linsrc.weight, self.lintgt.weight, t
@@ -319,7 +323,10 @@ class NodeModelGatedAdditive(NodeModelAdditive):
     NodeModelAdditive (``num_edges`` in ``**kwargs`` for 'free').  ``x @ W``
     runs on :func:`mgcn.ops.linear`, the gate, the gather, the reduce, bias
     and ReLU on :func:`mgcn.ops.gate_aggregate`; the gate needs the projected
-    rows themselves, so the layer is never reassociated to ``(A x) W``."""
+    rows themselves, so the layer is never reassociated to ``(A x) W``.  A
+    bfloat16 ``x`` keeps bf16 rows through the gate kernels (fp32 master
+    parameters, or the module after ``.to(torch.bfloat16)``) and gives a
+    bfloat16 output; the gates stay fp32."""
 
     _gated = True
 

@@ -37,8 +37,8 @@ from .ops_gemm import (SMALL_K, VENDOR_GEMMS, _Bmm, _bstr, _gemm_batched,  # noq
 from .ops_attention import (_AttentionAggregate, _HardAttentionEval,  # noqa: F401
                             _HardAttentionTrain, attention_aggregate,
                             hard_attention_aggregate)
-from .ops_gate import (_GateAggregate, gate_aggregate, gate_heavy_rows,  # noqa: F401
-                       set_gate_heavy_rows)
+from .ops_gate import (_GateAggregate, _GateAggregateBf16, gate_aggregate,  # noqa: F401
+                       gate_heavy_rows, set_gate_heavy_rows)
 from .ops_multi import (_MultiAggregate, multi_aggregate, multi_kernel_fusable,  # noqa: F401
                         multi_kernel_reason, multi_spmm_bwd, multi_spmm_fwd)
 from .ops_bf16 import (ROW_COPIES, _AggregateBf16, _LayerXWBf16, _SegmentReduceBf16,  # noqa: F401
