@@ -1357,6 +1357,108 @@ int mgcn_gate_bwd_src_sched_bf16(int64_t n_rows, int64_t nnz, int32_t C,
                                  const float *cnt, const int32_t *order, int64_t n_heavy,
                                  int64_t n_giant, float *coef, void *stream);
 
+/* ---------------------------------------- attention launches, heavy rows */
+
+/*
+ * The fp32 attention launches, soft and hard, with the row schedule of the
+ * view they walk (mgcn_row_schedule: order, n_heavy, n_giant; the fwd view's
+ * for the _fwd_sched and _bwd_dst_sched entries, the bwd view's for the
+ * _edge_softmax_sched and _bwd_src_sched ones).  Backward-compatible
+ * additions: MGCN_ABI_VERSION stays 22.  Each entry has the arguments of the
+ * entry without a schedule, with (order, n_heavy, n_giant[, coef]) before the
+ * stream.
+ *
+ * The rows order[0, n_heavy) -- a hub of several thousand edges would hold
+ * one wave for the whole launch -- go to workgroups (the first n_giant of
+ * them to the larger workgroup); the rows order[n_heavy, n_rows) stay on the
+ * wave-per-row kernels.  Every output element (Y, alpha, dz, ds_row, ds_src,
+ * dHp) has exactly the bits the entry without a schedule gives it: what a
+ * (slot, head) contributes is formed by any thread, what a row sums is
+ * summed in the wave kernel's order (its per-lane chains over the slots
+ * c G + kl, its serial S chains, one chain per feature in slot order for the
+ * gathers).  No atomics, no hand-off between workgroups; every launch is on
+ * `stream`; the library allocates nothing.
+ *
+ *   _fwd_sched           one workgroup per heavy row: row max, sum exp,
+ *                        alpha, coef = alpha mask, the weighted gather
+ *                        (alpha_in given: coef and the gather only)
+ *   _edge_softmax_sched  the same without the gather
+ *   _bwd_dst_sched       the row's slots spread over waves (per-slot dots,
+ *                        dz = mask dalpha'), then under softmax one
+ *                        workgroup per row (S, the edge phase, ds_row)
+ *   _bwd_src_sched       one workgroup per heavy row of the bwd view: coef,
+ *                        S, under softmax the adjoint in place and ds_src,
+ *                        the gather, the two rank-one terms
+ *
+ * coef is the caller's scratch of nnz H floats (alpha mask of every (slot,
+ * head) of a heavy row, in the slot order of the view walked; its contents
+ * after the call are unspecified); required whenever order is given and
+ * nnz > 0.  The edge softmax and the adjoint by destination need none and do
+ * not take it.  order == NULL: exactly the entry without a schedule
+ * (n_heavy, n_giant and coef are not read).  With order given,
+ * 0 <= n_giant <= n_heavy <= n_rows, else MGCN_EINVAL; like every other
+ * argument error, before any launch.  order holds each row of [0, n_rows)
+ * once.
+ *
+ * Kept on one wave per row: the _bf16 entries, mgcn_att_dst_fold,
+ * mgcn_hatt_select / mgcn_hatt_gather, mgcn_att_scores (per node).
+ */
+int mgcn_att_fwd_sched(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr,
+                       const int32_t *col, const float *s_row, const float *s_col, int act,
+                       const float *alpha_in, const float *mask, const float *Hp, int64_t ldh,
+                       float *Y, int64_t ldy, float *alpha, const int32_t *order,
+                       int64_t n_heavy, int64_t n_giant, float *coef, void *stream);
+
+int mgcn_edge_softmax_sched(int64_t n_rows, int64_t nnz, int32_t H, const int64_t *rowptr,
+                            const int32_t *col, const float *s_row, const float *s_col, int act,
+                            float *alpha, const int32_t *order, int64_t n_heavy,
+                            int64_t n_giant, void *stream);
+
+int mgcn_att_bwd_dst_sched(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                           const int64_t *rowptr, const int32_t *col, const float *Hp,
+                           int64_t ldh, const float *dY, int64_t lddy, const float *alpha,
+                           const float *mask, const float *s_row, const float *s_col, int act,
+                           int softmax, float *dz, float *ds_row, const int32_t *order,
+                           int64_t n_heavy, int64_t n_giant, void *stream);
+
+int mgcn_att_bwd_src_sched(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                           const int64_t *rowptr_t, const int32_t *col_t,
+                           const int32_t *slot_map, const float *dY, int64_t lddy,
+                           const float *alpha, const float *mask, float *dz, const float *s_row,
+                           const float *s_col, int act, int softmax, const float *a,
+                           const float *ds_dst, float *ds_src, float *dHp, int64_t lddh,
+                           const int32_t *order, int64_t n_heavy, int64_t n_giant, float *coef,
+                           void *stream);
+
+int mgcn_hatt_fwd_sched(int64_t n_rows, int64_t nnz, int32_t H, int32_t C, const int64_t *rowptr,
+                        const int32_t *col, const float *s_row, const float *s_col, int act,
+                        const float *noise, float temperature, const float *alpha_in,
+                        const float *mask, const float *Hp, int64_t ldh, float *Y, int64_t ldy,
+                        float *alpha, const int32_t *order, int64_t n_heavy, int64_t n_giant,
+                        float *coef, void *stream);
+
+int mgcn_hatt_edge_softmax_sched(int64_t n_rows, int64_t nnz, int32_t H, const int64_t *rowptr,
+                                 const int32_t *col, const float *s_row, const float *s_col,
+                                 int act, const float *noise, float temperature, float *alpha,
+                                 const int32_t *order, int64_t n_heavy, int64_t n_giant,
+                                 void *stream);
+
+int mgcn_hatt_bwd_dst_sched(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                            const int64_t *rowptr, const int32_t *col, const float *Hp,
+                            int64_t ldh, const float *dY, int64_t lddy, const float *alpha,
+                            const float *mask, const float *s_row, const float *s_col, int act,
+                            int softmax, float temperature, float *dz, float *ds_row,
+                            const int32_t *order, int64_t n_heavy, int64_t n_giant, void *stream);
+
+int mgcn_hatt_bwd_src_sched(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
+                            const int64_t *rowptr_t, const int32_t *col_t,
+                            const int32_t *slot_map, const float *dY, int64_t lddy,
+                            const float *alpha, const float *mask, float *dz, const float *s_row,
+                            const float *s_col, int act, int softmax, float temperature,
+                            const float *a, const float *ds_dst, float *ds_src, float *dHp,
+                            int64_t lddh, const int32_t *order, int64_t n_heavy, int64_t n_giant,
+                            float *coef, void *stream);
+
 /* --------------------------------------------------- multi-kernel layers */
 
 /*

@@ -141,6 +141,7 @@ struct FwdArgsT {
   int64_t ldy;
   float *alpha;
   static constexpr bool kHard = false;
+  static constexpr bool kSched = false;
 };
 using FwdArgs = FwdArgsT<float>;
 
@@ -154,6 +155,18 @@ struct HardFwdArgsT : FwdArgsT<R> {
   static constexpr bool kHard = true;
 };
 using HardFwdArgs = HardFwdArgsT<float>;
+
+// Any argument struct B of the three kernels below with a row schedule
+// (mgcn_row_schedule): the kernel walks the rows order[n_heavy, n_rows) in
+// that order instead of [0, n_rows); the heavy rows order[0, n_heavy) are
+// attention_heavy.hip's.  Without it (kSched false) the kernels are the code
+// they always were.
+template <class B>
+struct SchedArgsT : B {
+  const int32_t *order;
+  int64_t n_heavy;
+  static constexpr bool kSched = true;
+};
 
 // The logit of (slot, head) idx from its pre-activation z.
 template <bool HARD>
@@ -193,7 +206,11 @@ __global__ __launch_bounds__(kAttThreads) void att_fwd_kernel(A a) {
     noise = a.noise;
     T = a.temperature;
   }
-  for (int64_t row = wave0; row < a.n_rows; row += nwaves) {
+  int64_t n_work = a.n_rows;
+  if constexpr (A::kSched) n_work -= a.n_heavy;
+  for (int64_t ri = wave0; ri < n_work; ri += nwaves) {
+    int64_t row = ri;
+    if constexpr (A::kSched) row = a.order[a.n_heavy + ri];
     const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
     float m = -1e16f, denom = 1.0f, sr = 0.0f;
     if (a.alpha_in == nullptr) {
@@ -286,6 +303,7 @@ struct BwdDstArgsT {
   const float *alpha, *mask, *s_row, *s_col;
   float *dz, *ds_row;
   static constexpr bool kHard = false;
+  static constexpr bool kSched = false;
 };
 using BwdDstArgs = BwdDstArgsT<float>;
 
@@ -309,7 +327,11 @@ __global__ __launch_bounds__(kAttThreads) void att_bwd_dst_kernel(A a) {
   feature_heads<FPL>(hf, lane, HC, a.C);
   float T = 1.0f;
   if constexpr (A::kHard) T = a.temperature;
-  for (int64_t row = wave0; row < a.n_rows; row += nwaves) {
+  int64_t n_work = a.n_rows;
+  if constexpr (A::kSched) n_work -= a.n_heavy;
+  for (int64_t ri = wave0; ri < n_work; ri += nwaves) {
+    int64_t row = ri;
+    if constexpr (A::kSched) row = a.order[a.n_heavy + ri];
     float dy[FPL];
 #pragma unroll
     for (int i = 0; i < FPL; ++i) {
@@ -388,6 +410,7 @@ struct BwdSrcArgsT {
   int64_t lddh;
   static constexpr bool kHard = false;
   static constexpr bool kPark = false;
+  static constexpr bool kSched = false;
 };
 using BwdSrcArgs = BwdSrcArgsT<float>;
 
@@ -420,7 +443,11 @@ __global__ __launch_bounds__(kAttThreads) void att_bwd_src_kernel(A a) {
   feature_heads<FPL>(hf, lane, HC, a.C);
   float T = 1.0f;
   if constexpr (A::kHard) T = a.temperature;
-  for (int64_t row = wave0; row < a.n_rows; row += nwaves) {
+  int64_t n_work = a.n_rows;
+  if constexpr (A::kSched) n_work -= a.n_heavy;
+  for (int64_t ri = wave0; ri < n_work; ri += nwaves) {
+    int64_t row = ri;
+    if constexpr (A::kSched) row = a.order[a.n_heavy + ri];
     const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
     float acc[FPL];
 #pragma unroll

@@ -12,7 +12,9 @@
 // exist here: the per-edge state is alpha [nnz, H] (and dz in the backward).
 //
 // Work split (all kernels: 4 waves per workgroup, one wave per CSR row,
-// grid-stride over rows, a row of any degree walked in chunks):
+// grid-stride over rows, a row of any degree walked in chunks; the _sched
+// entries of attention_heavy.hip take the rows of more than 128 edges of the
+// fp32 launches to workgroups instead, with the same bits):
 //  * feature phase: lane l holds features f = l + 64 i (i < FPL) of the row's
 //    H C wide vector, so every gathered row is read coalesced; the head of a
 //    feature is f / C (any C).  Per-head dot products sum the lane's own

@@ -221,6 +221,28 @@ SIGNATURES = {
     "mgcn_gate_bwd_src_sched_bf16": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                             _i64, _i64, _vp, _vp]),
+    # the fp32 attention launches + (order, n_heavy, n_giant[, coef scratch])
+    # before the stream (edge_softmax and bwd_dst take no scratch)
+    "mgcn_att_fwd_sched": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp,
+                                  _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "mgcn_edge_softmax_sched": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _vp, _i64,
+                                       _i64, _vp]),
+    "mgcn_att_bwd_dst_sched": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                      _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "mgcn_att_bwd_src_sched": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                      _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _i64, _vp,
+                                      _i64, _i64, _vp, _vp]),
+    "mgcn_hatt_fwd_sched": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _int, _vp, _f32,
+                                   _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp,
+                                   _vp]),
+    "mgcn_hatt_edge_softmax_sched": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _int, _vp, _f32,
+                                            _vp, _vp, _i64, _i64, _vp]),
+    "mgcn_hatt_bwd_dst_sched": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                       _vp, _vp, _vp, _int, _int, _f32, _vp, _vp, _vp, _i64, _i64,
+                                       _vp]),
+    "mgcn_hatt_bwd_src_sched": (_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                       _vp, _vp, _vp, _int, _int, _f32, _vp, _vp, _vp, _vp, _i64,
+                                       _vp, _i64, _i64, _vp, _vp]),
     "mgcn_multi_spmm_fwd": (_int, [_i64, _i32, _i32, MultiViewsC, _vp, _i64, _vp, _i64, _int, _int,
                                    _int, _vp]),
     "mgcn_multi_spmm_bwd": (_int, [_i64, _i32, _i32, MultiViewsC, _vp, _i64, _vp, _i64, _int, _int,

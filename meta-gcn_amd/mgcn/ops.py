@@ -36,7 +36,8 @@ from .ops_gemm import (SMALL_K, VENDOR_GEMMS, _Bmm, _bstr, _gemm_batched,  # noq
                        relu_bwd_colsum)
 from .ops_attention import (_AttentionAggregate, _HardAttentionEval,  # noqa: F401
                             _HardAttentionTrain, attention_aggregate,
-                            hard_attention_aggregate)
+                            attention_heavy_rows, hard_attention_aggregate,
+                            set_attention_heavy_rows)
 from .ops_gate import (_GateAggregate, _GateAggregateBf16, gate_aggregate,  # noqa: F401
                        gate_heavy_rows, set_gate_heavy_rows)
 from .ops_multi import (_MultiAggregate, multi_aggregate, multi_kernel_fusable,  # noqa: F401

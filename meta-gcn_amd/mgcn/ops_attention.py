@@ -8,8 +8,17 @@ Feature rows are fp32 or bf16 (``Hp.dtype``).  A bf16 ``Hp`` takes the
 alpha, the mask, the noise, dz, ds and the attention vector stay fp32.
 Contract ("bf16 attention rows"): every fp32 output has the bits of
 the fp32 path on ``Hp.float()`` / ``dY.float()``, every bf16 output those bits
-rounded once to nearest even."""
+rounded once to nearest even.
+
+Heavy rows ("Attention", "Heavy rows"): an fp32 launch over a
+view whose row schedule has heavy rows (degree > 128) goes through the
+``mgcn_*_sched`` sibling of its entry, which sends those rows to workgroups
+and changes no bit (:func:`set_attention_heavy_rows`; timer names are
+unchanged).  bf16 rows, ``att_dst_fold`` and the eval forward keep one wave
+per row."""
 from __future__ import annotations
+
+import os
 
 import torch
 
@@ -19,6 +28,27 @@ from .graph import GraphPlan
 from .ops_gemm import gemm_tn
 
 BF16 = torch.bfloat16
+
+
+# heavy rows (degree > 128, graph.schedule_rows) of the fp32 attention launches
+# by workgroups (the mgcn_(h)att_*_sched entries, bit-identical to the
+# wave-per-row launches); MGCN_ATT_HEAVY=0 keeps one wave per row for every row
+_ATT_HEAVY = os.environ.get("MGCN_ATT_HEAVY", "1") != "0"
+
+
+def set_attention_heavy_rows(enabled: bool) -> None:
+    """Send (True, the default) the heavy rows of the fp32 attention launches
+    (soft and hard: fwd, edge_softmax, bwd_dst, bwd_src) through the workgroup
+    path of the ``mgcn_*_sched`` entries, or keep (False; env
+    MGCN_ATT_HEAVY=0) one wave per row for every row.  Results are bitwise the
+    same either way."""
+    global _ATT_HEAVY
+    _ATT_HEAVY = bool(enabled)
+
+
+def attention_heavy_rows() -> bool:
+    """The switch :func:`set_attention_heavy_rows` sets."""
+    return _ATT_HEAVY
 
 
 def _require_row_dtype(t: torch.Tensor, name: str) -> None:
@@ -54,6 +84,26 @@ def _row_launch(lib, name: str, bf16: bool, dev, rows, edges, *args) -> None:
     launch(name, "mgcn_" + name, dev, rows, edges, getattr(lib, "mgcn_" + name), *args)
 
 
+def _view_launch(lib, name: str, bf16: bool, dev, rows, view, nnz: int, H: int, scratch: bool,
+                 *args, bf16_rows: bool = False) -> None:
+    """A launch of entry ``name`` that walks ``view`` (args up to the stream,
+    which comes last): for fp32 rows over a view with heavy rows, with the
+    switch on, its ``mgcn_<name>_sched`` sibling with the view's schedule (and
+    a coef scratch [nnz, H] from torch's allocator where the entry takes one),
+    under the same timer name; else :func:`_row_launch`.  ``bf16_rows``: a
+    launch that touches no feature row (no ``_bf16`` sibling) of an op on bf16
+    rows, which keeps the wave launches throughout."""
+    if bf16 or bf16_rows or not (_ATT_HEAVY and view.order is not None and view.n_heavy > 0):
+        _row_launch(lib, name, bf16, dev, rows, view.edges, *args)
+        return
+    sched = (L.ptr(view.order), view.n_heavy, view.n_giant)
+    if scratch:
+        coef = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+        sched += (L.ptr(coef),)
+    sym = "mgcn_" + name + "_sched"
+    launch(name, sym, dev, rows, view.edges, getattr(lib, sym), *args[:-1], *sched, args[-1])
+
+
 def _att_f32(att_weight: torch.Tensor, H: int, C: int) -> torch.Tensor:
     """The attention vector as fp32 [H, 2C]; a bf16 one (a module after
     ``.to(torch.bfloat16)``) is cast through autograd, so its gradient comes
@@ -85,12 +135,13 @@ def _bwd_src_fold(lib, hard_T, bf16, inn, plan, H, C, act, dY, alpha, mask, dz, 
     slot = plan.slot_map() if nnz else None
     dHp = torch.empty(N, HC, dtype=dY.dtype, device=dev)
     park = torch.empty(N, HC, dtype=torch.float32, device=dev) if bf16 and not inn else None
-    _row_launch(lib, "att_bwd_src" if hard_T is None else "hatt_bwd_src", bf16, dev, N, bwd.edges,
-                N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
-                dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
-                act, int(not inn), *(() if hard_T is None else (hard_T,)), L.ptr(att),
-                L.ptr(ds_dst) if inn else None, L.ptr(ds_src), L.ptr(dHp), HC,
-                *((L.ptr(park),) if bf16 else ()), st)
+    _view_launch(lib, "att_bwd_src" if hard_T is None else "hatt_bwd_src", bf16, dev, N, bwd,
+                 nnz, H, True,
+                 N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
+                 dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
+                 act, int(not inn), *(() if hard_T is None else (hard_T,)), L.ptr(att),
+                 L.ptr(ds_dst) if inn else None, L.ptr(ds_src), L.ptr(dHp), HC,
+                 *((L.ptr(park),) if bf16 else ()), st)
     if not inn:
         _row_launch(lib, "att_dst_fold", bf16, dev, N, fwd.edges,
                     N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(dz), L.ptr(att), L.ptr(ds_dst),
@@ -131,20 +182,21 @@ class _AttentionAggregate(torch.autograd.Function):
         _row_launch(lib, "att_scores", bf, dev, N, None,
                     N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
         if att_dir == 'in' or nnz == 0:
-            _row_launch(lib, "att_fwd", bf, dev, N, fwd.edges,
-                        N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst),
-                        L.ptr(s_src), act, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y),
-                        HC, L.ptr(alpha), st)
+            _view_launch(lib, "att_fwd", bf, dev, N, fwd, nnz, H, True,
+                         N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst),
+                         L.ptr(s_src), act, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y),
+                         HC, L.ptr(alpha), st)
         else:
             a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-            launch("edge_softmax", "mgcn_edge_softmax", dev, N, bwd.edges, lib.mgcn_edge_softmax,
-                   N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
-                   L.ptr(a_bwd), st)
+            _view_launch(lib, "edge_softmax", False, dev, N, bwd, nnz, H, False,
+                         N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src),
+                         L.ptr(s_dst), act,
+                         L.ptr(a_bwd), st, bf16_rows=bf)
             alpha[plan.slot_map()[:nnz].long()] = a_bwd
-            _row_launch(lib, "att_fwd", bf, dev, N, fwd.edges,
-                        N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act,
-                        L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None,
-                        st)
+            _view_launch(lib, "att_fwd", bf, dev, N, fwd, nnz, H, True,
+                         N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act,
+                         L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None,
+                         st)
         ctx.plan, ctx.H, ctx.act, ctx.att_dir = plan, H, act, att_dir
         ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
         ctx.mark_non_differentiable(alpha)
@@ -167,10 +219,10 @@ class _AttentionAggregate(torch.autograd.Function):
         ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
         ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
         inn = ctx.att_dir == 'in'
-        _row_launch(lib, "att_bwd_dst", bf, dev, N, fwd.edges,
-                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
-                    L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst),
-                    L.ptr(s_src), act, int(inn), L.ptr(dz), L.ptr(ds_dst), st)
+        _view_launch(lib, "att_bwd_dst", bf, dev, N, fwd, nnz, H, False,
+                     N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
+                     L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst),
+                     L.ptr(s_src), act, int(inn), L.ptr(dz), L.ptr(ds_dst), st)
         dHp = _bwd_src_fold(lib, None, bf, inn, plan, H, C, act, dY, alpha, mask, dz, s_src, s_dst,
                             att, ds_dst, ds_src, st)
         datt = _datt(ds_src, ds_dst, Hp, H, C) if ctx.needs_input_grad[1] else None
@@ -257,21 +309,21 @@ class _HardAttentionTrain(torch.autograd.Function):
         _row_launch(lib, "att_scores", bf, dev, N, None,
                     N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
         if att_dir == 'in' or nnz == 0:
-            _row_launch(lib, "hatt_fwd", bf, dev, N, fwd.edges,
-                        N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst),
-                        L.ptr(s_src), act, L.ptr(noise), T, None, L.ptr(mask), L.ptr(Hp),
-                        Hp.stride(0), L.ptr(Y), HC, L.ptr(alpha), st)
+            _view_launch(lib, "hatt_fwd", bf, dev, N, fwd, nnz, H, True,
+                         N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst),
+                         L.ptr(s_src), act, L.ptr(noise), T, None, L.ptr(mask), L.ptr(Hp),
+                         Hp.stride(0), L.ptr(Y), HC, L.ptr(alpha), st)
         else:
             a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-            launch("hatt_edge_softmax", "mgcn_hatt_edge_softmax", dev, N, bwd.edges,
-                   lib.mgcn_hatt_edge_softmax,
-                   N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src), L.ptr(s_dst), act,
-                   L.ptr(noise), T, L.ptr(a_bwd), st)
+            _view_launch(lib, "hatt_edge_softmax", False, dev, N, bwd, nnz, H, False,
+                         N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src),
+                         L.ptr(s_dst), act,
+                         L.ptr(noise), T, L.ptr(a_bwd), st, bf16_rows=bf)
             alpha[plan.slot_map()[:nnz].long()] = a_bwd
-            _row_launch(lib, "hatt_fwd", bf, dev, N, fwd.edges,
-                        N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act, None, T,
-                        L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None,
-                        st)
+            _view_launch(lib, "hatt_fwd", bf, dev, N, fwd, nnz, H, True,
+                         N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act, None, T,
+                         L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None,
+                         st)
         ctx.plan, ctx.H, ctx.act, ctx.att_dir, ctx.T = plan, H, act, att_dir, T
         ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
         ctx.mark_non_differentiable(alpha)
@@ -294,10 +346,10 @@ class _HardAttentionTrain(torch.autograd.Function):
         ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
         ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
         inn = ctx.att_dir == 'in'
-        _row_launch(lib, "hatt_bwd_dst", bf, dev, N, fwd.edges,
-                    N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
-                    L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst),
-                    L.ptr(s_src), act, int(inn), T, L.ptr(dz), L.ptr(ds_dst), st)
+        _view_launch(lib, "hatt_bwd_dst", bf, dev, N, fwd, nnz, H, False,
+                     N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
+                     L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst),
+                     L.ptr(s_src), act, int(inn), T, L.ptr(dz), L.ptr(ds_dst), st)
         dHp = _bwd_src_fold(lib, T, bf, inn, plan, H, C, act, dY, alpha, mask, dz, s_src, s_dst,
                             att, ds_dst, ds_src, st)
         datt = _datt(ds_src, ds_dst, Hp, H, C) if ctx.needs_input_grad[1] else None
@@ -375,11 +427,11 @@ class _HardAttentionEval(torch.autograd.Function):
         dz = torch.zeros(nnz, H, dtype=torch.float32, device=dev)
         ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
         dHp = torch.empty(N, HC, dtype=dY.dtype, device=dev)
-        _row_launch(lib, "att_bwd_src", bf, dev, N, bwd.edges,
-                    N, nnz, H, HC // H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
-                    dY.stride(0), L.ptr(alpha), None, L.ptr(dz), None, None, 0, 0, L.ptr(att),
-                    None, L.ptr(ds_src), L.ptr(dHp), HC, *((None,) if bf else ()),
-                    L.stream_of(dev))
+        _view_launch(lib, "att_bwd_src", bf, dev, N, bwd, nnz, H, True,
+                     N, nnz, H, HC // H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
+                     dY.stride(0), L.ptr(alpha), None, L.ptr(dz), None, None, 0, 0, L.ptr(att),
+                     None, L.ptr(ds_src), L.ptr(dHp), HC, *((None,) if bf else ()),
+                     L.stream_of(dev))
         return dHp, None, None, None, None, None, None
 
 
