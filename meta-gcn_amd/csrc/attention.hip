@@ -37,13 +37,15 @@
 //
 // The lane-layout helpers, the softmax + gather kernel and the two adjoint
 // kernels live in attention.h, shared with hard_attention.hip; the scores and
-// fold kernels and the soft C entries are here.
+// fold kernels and the soft C entries are here.  The entries that walk a view
+// (fwd, edge_softmax, bwd_dst, bwd_src) fill an argument struct and call the
+// operation's checked body in attention_entry.h.
 //
 // Every entry that reads or writes a feature row has a _bf16 sibling over
 // bf16 rows (the contract at the top of attention.h); the two share one
-// templated body and one kernel source, instantiated per row type.
+// kernel source, instantiated per row type.
 
-#include "attention.h"
+#include "attention_entry.h"
 
 namespace mgcn {
 namespace {
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(kAttThreads) void att_dst_fold_bf16_kernel(
                               lddh);
 }
 
-// ------------------------------------------- entry bodies, per row type R
+// ------------------------------------------- entry body, per row type R
 template <class R>
 int att_scores(const char *fn, int64_t n, int32_t H, int32_t C, const R *Hp, int64_t ldh,
                const float *a, float *s_src, float *s_dst, void *stream) {
@@ -157,86 +159,6 @@ int att_scores(const char *fn, int64_t n, int32_t H, int32_t C, const R *Hp, int
   ATT_DISPATCH(H * C, CALL);
 #undef CALL
   return check_launch("att_scores_kernel");
-}
-
-template <class R>
-int att_fwd(const char *fn, int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
-            const int64_t *rowptr, const int32_t *col, const float *s_row, const float *s_col,
-            int act, const float *alpha_in, const float *mask, const R *Hp, int64_t ldh, R *Y,
-            int64_t ldy, float *alpha, void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C);
-  ATT_ACT_OK(fn, act);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hp && Y, "%s: null array", fn);
-  MGCN_REQUIRE(nnz == 0 || col, "%s: null col", fn);
-  MGCN_REQUIRE(alpha_in != nullptr || (s_row && s_col && (alpha || nnz == 0)),
-               "%s: need alpha_in, or s_row / s_col / alpha", fn);
-  MGCN_REQUIRE(ldh >= (int64_t)H * C && ldy >= (int64_t)H * C,
-               "%s: leading dimension too small", fn);
-  FwdArgsT<R> k{n_rows, H, C, act, rowptr, col, s_row, s_col, alpha_in, mask, Hp, ldh, Y, ldy,
-                alpha};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                       \
-  hipLaunchKernelGGL((att_fwd_kernel<FPL, true, FwdArgsT<R>>), dim3(att_grid(n_rows)), \
-                     dim3(kAttThreads), 0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_fwd_kernel");
-}
-
-template <class R>
-int att_bwd_dst(const char *fn, int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
-                const int64_t *rowptr, const int32_t *col, const R *Hp, int64_t ldh, const R *dY,
-                int64_t lddy, const float *alpha, const float *mask, const float *s_row,
-                const float *s_col, int act, int softmax, float *dz, float *ds_row,
-                void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C);
-  ATT_ACT_OK(fn, act);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hp && dY, "%s: null array", fn);
-  MGCN_REQUIRE(nnz == 0 || (col && dz), "%s: null col / dz", fn);
-  MGCN_REQUIRE(!softmax || (ds_row && s_row && s_col && (alpha || nnz == 0)),
-               "%s: the softmax adjoint needs alpha, s_row, s_col, ds_row", fn);
-  MGCN_REQUIRE(ldh >= (int64_t)H * C && lddy >= (int64_t)H * C,
-               "%s: leading dimension too small", fn);
-  BwdDstArgsT<R> k{n_rows, H, C, act, softmax ? 1 : 0, rowptr, col, Hp, ldh, dY, lddy,
-                   alpha, mask, s_row, s_col, dz, ds_row};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                        \
-  hipLaunchKernelGGL((att_bwd_dst_kernel<FPL, BwdDstArgsT<R>>), dim3(att_grid(n_rows)), \
-                     dim3(kAttThreads), 0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_bwd_dst_kernel");
-}
-
-// A: BwdSrcArgs or BwdSrcArgsBf16, filled by the caller
-template <class A>
-int att_bwd_src(const char *fn, const A &k, int64_t nnz, void *stream) {
-  clear_error();
-  const int H = k.H, C = k.C;
-  ATT_REQUIRE_SHAPE(fn, k.n_rows, nnz, H, C);
-  ATT_ACT_OK(fn, k.act);
-  if (k.n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(k.rowptr && k.dY && k.a && k.ds_src, "%s: null array", fn);
-  MGCN_REQUIRE(nnz == 0 || (k.col && k.slot && k.alpha && k.dz),
-               "%s: null col / slot_map / alpha / dz", fn);
-  MGCN_REQUIRE(!k.softmax || (k.s_row && k.s_col), "%s: the softmax adjoint needs s_row, s_col",
-               fn);
-  bool parked = false;
-  if constexpr (A::kPark) parked = k.dHp_f32 != nullptr;
-  MGCN_REQUIRE(parked || k.dHp, "%s: null dHp", fn);
-  MGCN_REQUIRE(k.lddy >= (int64_t)H * C && (parked || k.lddh >= (int64_t)H * C),
-               "%s: leading dimension too small", fn);
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                         \
-  hipLaunchKernelGGL((att_bwd_src_kernel<FPL, A>), dim3(att_grid(k.n_rows)), dim3(kAttThreads), \
-                     0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_bwd_src_kernel");
 }
 
 }  // namespace
@@ -260,8 +182,8 @@ extern "C" int mgcn_att_fwd(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
                             const float *s_col, int act, const float *alpha_in,
                             const float *mask, const float *Hp, int64_t ldh, float *Y,
                             int64_t ldy, float *alpha, void *stream) {
-  return att_fwd<float>("mgcn_att_fwd", n_rows, nnz, H, C, rowptr, col, s_row, s_col, act,
-                        alpha_in, mask, Hp, ldh, Y, ldy, alpha, stream);
+  FwdArgs k{n_rows, H, C, act, rowptr, col, s_row, s_col, alpha_in, mask, Hp, ldh, Y, ldy, alpha};
+  return fwd<true>("mgcn_att_fwd", k, nnz, "att_fwd_kernel", stream);
 }
 
 extern "C" int mgcn_att_fwd_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -269,23 +191,17 @@ extern "C" int mgcn_att_fwd_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t
                                  const float *s_col, int act, const float *alpha_in,
                                  const float *mask, const uint16_t *Hp, int64_t ldh, uint16_t *Y,
                                  int64_t ldy, float *alpha, void *stream) {
-  return att_fwd<uint16_t>("mgcn_att_fwd_bf16", n_rows, nnz, H, C, rowptr, col, s_row, s_col, act,
-                           alpha_in, mask, Hp, ldh, Y, ldy, alpha, stream);
+  FwdArgsT<uint16_t> k{n_rows, H, C, act, rowptr, col, s_row, s_col, alpha_in, mask, Hp, ldh, Y,
+                       ldy, alpha};
+  return fwd<true>("mgcn_att_fwd_bf16", k, nnz, "att_fwd_kernel", stream);
 }
 
 extern "C" int mgcn_edge_softmax(int64_t n_rows, int64_t nnz, int32_t H, const int64_t *rowptr,
                                  const int32_t *col, const float *s_row, const float *s_col,
                                  int act, float *alpha, void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE("mgcn_edge_softmax", n_rows, nnz, H, 1);
-  ATT_ACT_OK("mgcn_edge_softmax", act);
-  if (n_rows == 0 || nnz == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && col && s_row && s_col && alpha, "mgcn_edge_softmax: null array");
   FwdArgs k{n_rows, H, 1, act, rowptr, col, s_row, s_col, nullptr, nullptr, nullptr, 0,
             nullptr, 0, alpha};
-  hipLaunchKernelGGL((att_fwd_kernel<1, false>), dim3(att_grid(n_rows)), dim3(kAttThreads), 0,
-                     as_stream(stream), k);
-  return check_launch("att_fwd_kernel (softmax)");
+  return fwd<false>("mgcn_edge_softmax", k, nnz, "att_fwd_kernel (softmax)", stream);
 }
 
 extern "C" int mgcn_att_bwd_dst(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -293,8 +209,9 @@ extern "C" int mgcn_att_bwd_dst(int64_t n_rows, int64_t nnz, int32_t H, int32_t 
                                 int64_t ldh, const float *dY, int64_t lddy, const float *alpha,
                                 const float *mask, const float *s_row, const float *s_col,
                                 int act, int softmax, float *dz, float *ds_row, void *stream) {
-  return att_bwd_dst<float>("mgcn_att_bwd_dst", n_rows, nnz, H, C, rowptr, col, Hp, ldh, dY, lddy,
-                            alpha, mask, s_row, s_col, act, softmax, dz, ds_row, stream);
+  BwdDstArgs k{n_rows, H, C, act, softmax ? 1 : 0, rowptr, col, Hp, ldh, dY, lddy,
+               alpha, mask, s_row, s_col, dz, ds_row};
+  return bwd_dst("mgcn_att_bwd_dst", k, nnz, "att_bwd_dst_kernel", stream);
 }
 
 extern "C" int mgcn_att_bwd_dst_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -303,9 +220,9 @@ extern "C" int mgcn_att_bwd_dst_bf16(int64_t n_rows, int64_t nnz, int32_t H, int
                                      int64_t lddy, const float *alpha, const float *mask,
                                      const float *s_row, const float *s_col, int act, int softmax,
                                      float *dz, float *ds_row, void *stream) {
-  return att_bwd_dst<uint16_t>("mgcn_att_bwd_dst_bf16", n_rows, nnz, H, C, rowptr, col, Hp, ldh,
-                               dY, lddy, alpha, mask, s_row, s_col, act, softmax, dz, ds_row,
-                               stream);
+  BwdDstArgsT<uint16_t> k{n_rows, H, C, act, softmax ? 1 : 0, rowptr, col, Hp, ldh, dY, lddy,
+                          alpha, mask, s_row, s_col, dz, ds_row};
+  return bwd_dst("mgcn_att_bwd_dst_bf16", k, nnz, "att_bwd_dst_kernel", stream);
 }
 
 extern "C" int mgcn_att_bwd_src(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -317,7 +234,7 @@ extern "C" int mgcn_att_bwd_src(int64_t n_rows, int64_t nnz, int32_t H, int32_t 
                                 int64_t lddh, void *stream) {
   BwdSrcArgs k{n_rows, H, C, act, softmax ? 1 : 0, rowptr_t, col_t, slot_map, dY, lddy,
                alpha, mask, dz, s_row, s_col, a, ds_dst, ds_src, dHp, lddh};
-  return att_bwd_src("mgcn_att_bwd_src", k, nnz, stream);
+  return bwd_src("mgcn_att_bwd_src", k, nnz, "att_bwd_src_kernel", stream);
 }
 
 extern "C" int mgcn_att_bwd_src_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -330,7 +247,7 @@ extern "C" int mgcn_att_bwd_src_bf16(int64_t n_rows, int64_t nnz, int32_t H, int
   BwdSrcArgsBf16 k{{n_rows, H, C, act, softmax ? 1 : 0, rowptr_t, col_t, slot_map, dY, lddy,
                     alpha, mask, dz, s_row, s_col, a, ds_dst, ds_src, dHp, lddh},
                    dHp_f32};
-  return att_bwd_src("mgcn_att_bwd_src_bf16", k, nnz, stream);
+  return bwd_src("mgcn_att_bwd_src_bf16", k, nnz, "att_bwd_src_kernel", stream);
 }
 
 extern "C" int mgcn_att_dst_fold(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,

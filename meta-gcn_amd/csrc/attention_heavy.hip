@@ -34,21 +34,13 @@
 // heavy launches.  Barriers only: no atomics, no hand-off between workgroups;
 // separate launches are ordered by the stream.
 
-#include <atomic>
-
-#include "attention.h"
+#include "attention_entry.h"
 
 namespace mgcn {
 namespace {
 
 constexpr int kStage = 4096;  // floats of LDS a staged() batch may take
 constexpr int kStaticLds = 256;  // bytes kept out of the LDS budget for the kernels' static arrays
-
-struct HeavyRows {
-  const int32_t *order;
-  int64_t n_heavy, n_giant;
-  float *coef;
-};
 
 // A row's n = deg H terms, term(i) for i = (slot - beg) H + h, formed by all
 // HB threads batch after batch into stage[]; wave 0 consumes each batch with
@@ -423,19 +415,7 @@ GatherShape gather_shape(int HC, int budget) {
   return {FC, BE, lds};
 }
 
-// the 160 KB dynamic-LDS attribute is per device: one bit per device id, per
-// kernel; racing threads at worst both set it
-int allow_lds(const void *kernel, std::atomic<uint64_t> &attr_set) {
-  int dev = 0;
-  MGCN_HIP_TRY(hipGetDevice(&dev));
-  const uint64_t bit = uint64_t(1) << (dev & 63);
-  if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-    MGCN_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     160 * 1024 - kStaticLds));
-    attr_set.fetch_or(bit, std::memory_order_release);
-  }
-  return MGCN_OK;
-}
+constexpr int kMaxLds = 160 * 1024 - kStaticLds;  // dynamic LDS a heavy kernel may be given
 
 template <int HB, bool GATHER, class A>
 int launch_fwd_rows(const A &a, const int32_t *rows, int64_t n, float *coef, int budget,
@@ -444,7 +424,7 @@ int launch_fwd_rows(const A &a, const int32_t *rows, int64_t n, float *coef, int
   const GatherShape g = gather_shape(GATHER ? a.H * a.C : 1, budget);
   static std::atomic<uint64_t> attr_set{0};
   if (int rc = allow_lds(reinterpret_cast<const void *>(&att_fwd_heavy_kernel<HB, GATHER, A>),
-                         attr_set))
+                         attr_set, kMaxLds))
     return rc;
   hipLaunchKernelGGL((att_fwd_heavy_kernel<HB, GATHER, A>), dim3((unsigned)n), dim3(HB), g.lds, st,
                      a, rows, coef, g.FC, g.BE);
@@ -458,42 +438,19 @@ int launch_src_rows(const A &a, const int32_t *rows, int64_t n, float *coef, int
   const GatherShape g = gather_shape(a.H * a.C, budget);
   static std::atomic<uint64_t> attr_set{0};
   if (int rc = allow_lds(reinterpret_cast<const void *>(&att_bwd_src_heavy_kernel<HB, A>),
-                         attr_set))
+                         attr_set, kMaxLds))
     return rc;
   hipLaunchKernelGGL((att_bwd_src_heavy_kernel<HB, A>), dim3((unsigned)n), dim3(HB), g.lds, st, a,
                      rows, coef, g.FC, g.BE);
   return check_launch("att_bwd_src_heavy_kernel");
 }
 
-#define ATT_REQUIRE_SCHED(fn, s, n_rows)                                                     \
-  MGCN_REQUIRE(0 <= (s).n_giant && (s).n_giant <= (s).n_heavy && (s).n_heavy <= (n_rows),    \
-               "%s: need 0 <= n_giant <= n_heavy <= n_rows", fn)
-
-// A: FwdArgs or HardFwdArgs, validated as the entry without a schedule does.
+// The _sched bodies.  A: the argument struct of the entry without a schedule,
+// checked as that entry checks it (attention_entry.h) plus the schedule.
 // Heavy rows by workgroups, then the wave kernel over the schedule's rest.
 template <bool GATHER, class A>
 int fwd_sched(const char *fn, const A &k, int64_t nnz, const HeavyRows &s, void *stream) {
-  clear_error();
-  const int H = k.H, C = k.C;
-  ATT_REQUIRE_SHAPE(fn, k.n_rows, nnz, H, C);
-  ATT_ACT_OK(fn, k.act);
-  if constexpr (A::kHard)
-    MGCN_REQUIRE(k.temperature > 0.0f, "%s: need temperature > 0 (got %g)", fn,
-                 (double)k.temperature);
-  ATT_REQUIRE_SCHED(fn, s, k.n_rows);
-  if (k.n_rows == 0) return MGCN_OK;
-  if (GATHER) {
-    MGCN_REQUIRE(k.rowptr && k.Hp && k.Y, "%s: null array", fn);
-    MGCN_REQUIRE(nnz == 0 || k.col, "%s: null col", fn);
-    MGCN_REQUIRE(k.alpha_in != nullptr || (k.s_row && k.s_col && (k.alpha || nnz == 0)),
-                 "%s: need alpha_in, or s_row / s_col / alpha", fn);
-    MGCN_REQUIRE(k.ldh >= (int64_t)H * C && k.ldy >= (int64_t)H * C,
-                 "%s: leading dimension too small", fn);
-    MGCN_REQUIRE(nnz == 0 || s.coef, "%s: a schedule needs the coef scratch [nnz, H]", fn);
-  } else {
-    if (nnz == 0) return MGCN_OK;
-    MGCN_REQUIRE(k.rowptr && k.col && k.s_row && k.s_col && k.alpha, "%s: null array", fn);
-  }
+  ATT_CHECKED((fwd_check<GATHER>(fn, k, nnz, &s)));
   hipStream_t st = as_stream(stream);
   if (int rc = launch_fwd_rows<1024, GATHER>(k, s.order, s.n_giant, s.coef,
                                              g_opt.heavy_lds_kb * 1024, st))
@@ -501,39 +458,12 @@ int fwd_sched(const char *fn, const A &k, int64_t nnz, const HeavyRows &s, void 
   if (int rc = launch_fwd_rows<256, GATHER>(k, s.order + s.n_giant, s.n_heavy - s.n_giant, s.coef,
                                             g_opt.heavy_mid_lds_kb * 1024, st))
     return rc;
-  const int64_t n_work = k.n_rows - s.n_heavy;
-  if (n_work == 0) return MGCN_OK;
-  SchedArgsT<A> w{k, s.order, s.n_heavy};
-  if (GATHER) {
-#define CALL(FPL)                                                                              \
-  hipLaunchKernelGGL((att_fwd_kernel<FPL, true, SchedArgsT<A>>), dim3(att_grid(n_work)),      \
-                     dim3(kAttThreads), 0, st, w)
-    ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  } else {
-    hipLaunchKernelGGL((att_fwd_kernel<1, false, SchedArgsT<A>>), dim3(att_grid(n_work)),
-                       dim3(kAttThreads), 0, st, w);
-  }
-  return check_launch("att_fwd_kernel (schedule)");
+  return fwd_waves<GATHER>(SchedArgsT<A>{k, s.order, s.n_heavy}, "att_fwd_kernel (schedule)", st);
 }
 
 template <class A>
 int bwd_dst_sched(const char *fn, const A &k, int64_t nnz, const HeavyRows &s, void *stream) {
-  clear_error();
-  const int H = k.H, C = k.C;
-  ATT_REQUIRE_SHAPE(fn, k.n_rows, nnz, H, C);
-  ATT_ACT_OK(fn, k.act);
-  if constexpr (A::kHard)
-    MGCN_REQUIRE(k.temperature > 0.0f, "%s: need temperature > 0 (got %g)", fn,
-                 (double)k.temperature);
-  ATT_REQUIRE_SCHED(fn, s, k.n_rows);
-  if (k.n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(k.rowptr && k.Hp && k.dY, "%s: null array", fn);
-  MGCN_REQUIRE(nnz == 0 || (k.col && k.dz), "%s: null col / dz", fn);
-  MGCN_REQUIRE(!k.softmax || (k.ds_row && k.s_row && k.s_col && (k.alpha || nnz == 0)),
-               "%s: the softmax adjoint needs alpha, s_row, s_col, ds_row", fn);
-  MGCN_REQUIRE(k.ldh >= (int64_t)H * C && k.lddy >= (int64_t)H * C,
-               "%s: leading dimension too small", fn);
+  ATT_CHECKED(bwd_dst_check(fn, k, nnz, &s));
   hipStream_t st = as_stream(stream);
   // waves along y per row: a giant row's slot groups a few per wave, the
   // other heavy rows' (129 .. giant_thr slots) a handful
@@ -541,7 +471,7 @@ int bwd_dst_sched(const char *fn, const A &k, int64_t nnz, const HeavyRows &s, v
     if (n <= 0) return;
     const dim3 grid((unsigned)n, blocks_y), block(kAttThreads);
 #define CALL(FPL) hipLaunchKernelGGL((att_bwd_dst_slots_kernel<FPL, A>), grid, block, 0, st, k, rows)
-    ATT_DISPATCH(H * C, CALL);
+    ATT_DISPATCH(k.H * k.C, CALL);
 #undef CALL
   };
   slots(s.order, s.n_giant, 32);
@@ -552,52 +482,19 @@ int bwd_dst_sched(const char *fn, const A &k, int64_t nnz, const HeavyRows &s, v
                        0, st, k, s.order);
     if (int rc = check_launch("att_bwd_dst_row_kernel")) return rc;
   }
-  const int64_t n_work = k.n_rows - s.n_heavy;
-  if (n_work == 0) return MGCN_OK;
-  SchedArgsT<A> w{k, s.order, s.n_heavy};
-#define CALL(FPL)                                                                          \
-  hipLaunchKernelGGL((att_bwd_dst_kernel<FPL, SchedArgsT<A>>), dim3(att_grid(n_work)),    \
-                     dim3(kAttThreads), 0, st, w)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_bwd_dst_kernel (schedule)");
+  return bwd_dst_waves(SchedArgsT<A>{k, s.order, s.n_heavy}, "att_bwd_dst_kernel (schedule)", st);
 }
 
 template <class A>
 int bwd_src_sched(const char *fn, const A &k, int64_t nnz, const HeavyRows &s, void *stream) {
-  clear_error();
-  const int H = k.H, C = k.C;
-  ATT_REQUIRE_SHAPE(fn, k.n_rows, nnz, H, C);
-  ATT_ACT_OK(fn, k.act);
-  if constexpr (A::kHard)
-    MGCN_REQUIRE(k.temperature > 0.0f, "%s: need temperature > 0 (got %g)", fn,
-                 (double)k.temperature);
-  ATT_REQUIRE_SCHED(fn, s, k.n_rows);
-  if (k.n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(k.rowptr && k.dY && k.a && k.ds_src, "%s: null array", fn);
-  MGCN_REQUIRE(nnz == 0 || (k.col && k.slot && k.alpha && k.dz),
-               "%s: null col / slot_map / alpha / dz", fn);
-  MGCN_REQUIRE(!k.softmax || (k.s_row && k.s_col), "%s: the softmax adjoint needs s_row, s_col",
-               fn);
-  MGCN_REQUIRE(k.dHp, "%s: null dHp", fn);
-  MGCN_REQUIRE(k.lddy >= (int64_t)H * C && k.lddh >= (int64_t)H * C,
-               "%s: leading dimension too small", fn);
-  MGCN_REQUIRE(nnz == 0 || s.coef, "%s: a schedule needs the coef scratch [nnz, H]", fn);
+  ATT_CHECKED(bwd_src_check(fn, k, nnz, &s));
   hipStream_t st = as_stream(stream);
   if (int rc = launch_src_rows<1024>(k, s.order, s.n_giant, s.coef, g_opt.heavy_lds_kb * 1024, st))
     return rc;
   if (int rc = launch_src_rows<256>(k, s.order + s.n_giant, s.n_heavy - s.n_giant, s.coef,
                                     g_opt.heavy_mid_lds_kb * 1024, st))
     return rc;
-  const int64_t n_work = k.n_rows - s.n_heavy;
-  if (n_work == 0) return MGCN_OK;
-  SchedArgsT<A> w{k, s.order, s.n_heavy};
-#define CALL(FPL)                                                                          \
-  hipLaunchKernelGGL((att_bwd_src_kernel<FPL, SchedArgsT<A>>), dim3(att_grid(n_work)),    \
-                     dim3(kAttThreads), 0, st, w)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_bwd_src_kernel (schedule)");
+  return bwd_src_waves(SchedArgsT<A>{k, s.order, s.n_heavy}, "att_bwd_src_kernel (schedule)", st);
 }
 
 }  // namespace

@@ -262,38 +262,6 @@ int gate_vec(int32_t F, const void *p0, int64_t ld0, const void *p1, int64_t ld1
   return ok(4) ? 4 : ok(2) ? 2 : 1;
 }
 
-// the heavy-row body's launch shape (spmm.hip's launch_heavy_hb): feature
-// chunk FC, edge batch BE and the LDS they take out of `lds_budget` bytes
-struct HeavyShape {
-  int FC, BE;
-  size_t lds;
-};
-HeavyShape heavy_shape(int F, int VEC, int HB, int lds_budget) {
-  int FC = F < 128 ? F : 128;
-  FC = (FC + VEC - 1) / VEC * VEC;
-  const int producers = HB - 64 * ((FC + 63) / 64);
-  // 2 product buffers of FC x (BE + 4) floats + a 3-slot ring of 4 x BE words
-  int BE = (lds_budget / 4 - 8 * FC) / (2 * FC + 12);
-  if (BE > 4 * producers) BE = 4 * producers;
-  BE &= ~15;
-  if (BE < 16) BE = 16;
-  return {FC, BE, sizeof(float) * ((size_t)2 * FC * (BE + 4) + (size_t)12 * BE)};
-}
-
-// the 160 KB dynamic-LDS attribute is per device: one bit per device id, per
-// kernel; racing threads at worst both set it
-int allow_lds(const void *kernel, std::atomic<uint64_t> &attr_set) {
-  int dev = 0;
-  MGCN_HIP_TRY(hipGetDevice(&dev));
-  const uint64_t bit = uint64_t(1) << (dev & 63);
-  if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-    MGCN_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     160 * 1024));
-    attr_set.fetch_or(bit, std::memory_order_release);
-  }
-  return MGCN_OK;
-}
-
 template <int VEC, int MODE, int HB, class A>
 int launch_rows(SpmmArgs s, const A &a, const int32_t *rows, int64_t n, int lds_budget,
                 hipStream_t stream) {
@@ -303,7 +271,8 @@ int launch_rows(SpmmArgs s, const A &a, const int32_t *rows, int64_t n, int lds_
   static std::atomic<uint64_t> attr_set{0};
   if constexpr (MODE == FWD_SUM || MODE == FWD_MAX) {
     if (int rc = allow_lds(
-            reinterpret_cast<const void *>(&gate_fwd_heavy_kernel<VEC, MODE, HB, A>), attr_set))
+            reinterpret_cast<const void *>(&gate_fwd_heavy_kernel<VEC, MODE, HB, A>), attr_set,
+            160 * 1024))
       return rc;
     hipLaunchKernelGGL((gate_fwd_heavy_kernel<VEC, MODE, HB, A>), dim3((unsigned)n), dim3(HB),
                        h.lds, stream, s, a, h.FC, h.BE);
@@ -311,7 +280,7 @@ int launch_rows(SpmmArgs s, const A &a, const int32_t *rows, int64_t n, int lds_
   } else {
     if (int rc = allow_lds(
             reinterpret_cast<const void *>(&gate_bwd_src_heavy_kernel<VEC, MODE, HB, A>),
-            attr_set))
+            attr_set, 160 * 1024))
       return rc;
     hipLaunchKernelGGL((gate_bwd_src_heavy_kernel<VEC, MODE, HB, A>), dim3((unsigned)n),
                        dim3(HB), h.lds, stream, s, a, h.FC, h.BE);

@@ -4,8 +4,9 @@
 //
 // Training is soft attention with Gumbel noise and a temperature inside the
 // logit, l = (act(z) + g) / T: the kernels of attention.h instantiated with
-// the hard argument structs (the soft instantiations live in attention.hip,
-// a translation unit this file does not touch).  Eval replaces the softmax by
+// the hard argument structs through the checked bodies of attention_entry.h
+// (the soft instantiations live in attention.hip, a translation unit this
+// file does not touch).  Eval replaces the softmax by
 // a per-(row, head) argmax under torch_scatter's tie rule
 // (hatt_select_kernel) and the gather by one that loads only the rows of the
 // slots with a non-zero coefficient (hatt_gather_kernel): with a one-hot
@@ -15,7 +16,7 @@
 // The entries that touch a feature row have _bf16 siblings (the row type R of
 // attention.h); select and the edge softmax see fp32 scores alone.
 
-#include "attention.h"
+#include "attention_entry.h"
 
 namespace mgcn {
 namespace {
@@ -161,96 +162,7 @@ __global__ __launch_bounds__(kAttThreads) void hatt_gather_kernel(GatherArgsT<R>
   }
 }
 
-#define HATT_TEMPERATURE_OK(fn, T) \
-  MGCN_REQUIRE((T) > 0.0f, "%s: need temperature > 0 (got %g)", fn, (double)(T))
-
-// ------------------------------------------- entry bodies, per row type R
-template <class R>
-int hatt_fwd(const char *fn, int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
-             const int64_t *rowptr, const int32_t *col, const float *s_row, const float *s_col,
-             int act, const float *noise, float temperature, const float *alpha_in,
-             const float *mask, const R *Hp, int64_t ldh, R *Y, int64_t ldy, float *alpha,
-             void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C);
-  ATT_ACT_OK(fn, act);
-  HATT_TEMPERATURE_OK(fn, temperature);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hp && Y, "%s: null array", fn);
-  MGCN_REQUIRE(nnz == 0 || col, "%s: null col", fn);
-  MGCN_REQUIRE(alpha_in != nullptr || (s_row && s_col && (alpha || nnz == 0)),
-               "%s: need alpha_in, or s_row / s_col / alpha", fn);
-  MGCN_REQUIRE(ldh >= (int64_t)H * C && ldy >= (int64_t)H * C,
-               "%s: leading dimension too small", fn);
-  HardFwdArgsT<R> k{{n_rows, H, C, act, rowptr, col, s_row, s_col, alpha_in, mask, Hp, ldh, Y,
-                     ldy, alpha},
-                    noise, temperature};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                           \
-  hipLaunchKernelGGL((att_fwd_kernel<FPL, true, HardFwdArgsT<R>>), dim3(att_grid(n_rows)), \
-                     dim3(kAttThreads), 0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_fwd_kernel (hard)");
-}
-
-template <class R>
-int hatt_bwd_dst(const char *fn, int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
-                 const int64_t *rowptr, const int32_t *col, const R *Hp, int64_t ldh, const R *dY,
-                 int64_t lddy, const float *alpha, const float *mask, const float *s_row,
-                 const float *s_col, int act, int softmax, float temperature, float *dz,
-                 float *ds_row, void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE(fn, n_rows, nnz, H, C);
-  ATT_ACT_OK(fn, act);
-  HATT_TEMPERATURE_OK(fn, temperature);
-  if (n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && Hp && dY, "%s: null array", fn);
-  MGCN_REQUIRE(nnz == 0 || (col && dz), "%s: null col / dz", fn);
-  MGCN_REQUIRE(!softmax || (ds_row && s_row && s_col && (alpha || nnz == 0)),
-               "%s: the softmax adjoint needs alpha, s_row, s_col, ds_row", fn);
-  MGCN_REQUIRE(ldh >= (int64_t)H * C && lddy >= (int64_t)H * C,
-               "%s: leading dimension too small", fn);
-  HardBwdDstArgsT<R> k{{n_rows, H, C, act, softmax ? 1 : 0, rowptr, col, Hp, ldh, dY, lddy, alpha,
-                        mask, s_row, s_col, dz, ds_row},
-                       temperature};
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                            \
-  hipLaunchKernelGGL((att_bwd_dst_kernel<FPL, HardBwdDstArgsT<R>>), dim3(att_grid(n_rows)), \
-                     dim3(kAttThreads), 0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_bwd_dst_kernel (hard)");
-}
-
-// A: HardBwdSrcArgsT<BwdSrcArgs> or HardBwdSrcArgsT<BwdSrcArgsBf16>, filled by the caller
-template <class A>
-int hatt_bwd_src(const char *fn, const A &k, int64_t nnz, void *stream) {
-  clear_error();
-  const int H = k.H, C = k.C;
-  ATT_REQUIRE_SHAPE(fn, k.n_rows, nnz, H, C);
-  ATT_ACT_OK(fn, k.act);
-  HATT_TEMPERATURE_OK(fn, k.temperature);
-  if (k.n_rows == 0) return MGCN_OK;
-  MGCN_REQUIRE(k.rowptr && k.dY && k.a && k.ds_src, "%s: null array", fn);
-  MGCN_REQUIRE(nnz == 0 || (k.col && k.slot && k.alpha && k.dz),
-               "%s: null col / slot_map / alpha / dz", fn);
-  MGCN_REQUIRE(!k.softmax || (k.s_row && k.s_col), "%s: the softmax adjoint needs s_row, s_col",
-               fn);
-  bool parked = false;
-  if constexpr (A::kPark) parked = k.dHp_f32 != nullptr;
-  MGCN_REQUIRE(parked || k.dHp, "%s: null dHp", fn);
-  MGCN_REQUIRE(k.lddy >= (int64_t)H * C && (parked || k.lddh >= (int64_t)H * C),
-               "%s: leading dimension too small", fn);
-  hipStream_t s = as_stream(stream);
-#define CALL(FPL)                                                                         \
-  hipLaunchKernelGGL((att_bwd_src_kernel<FPL, A>), dim3(att_grid(k.n_rows)), dim3(kAttThreads), \
-                     0, s, k)
-  ATT_DISPATCH(H * C, CALL);
-#undef CALL
-  return check_launch("att_bwd_src_kernel (hard)");
-}
-
+// ------------------------------------------- entry body, per row type R
 template <class R>
 int hatt_gather(const char *fn, int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
                 const int64_t *rowptr, const int32_t *col, const float *alpha, const R *Hp,
@@ -282,8 +194,10 @@ extern "C" int mgcn_hatt_fwd(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
                              const float *s_col, int act, const float *noise, float temperature,
                              const float *alpha_in, const float *mask, const float *Hp,
                              int64_t ldh, float *Y, int64_t ldy, float *alpha, void *stream) {
-  return hatt_fwd<float>("mgcn_hatt_fwd", n_rows, nnz, H, C, rowptr, col, s_row, s_col, act,
-                         noise, temperature, alpha_in, mask, Hp, ldh, Y, ldy, alpha, stream);
+  HardFwdArgs k{{n_rows, H, C, act, rowptr, col, s_row, s_col, alpha_in, mask, Hp, ldh, Y, ldy,
+                 alpha},
+                noise, temperature};
+  return fwd<true>("mgcn_hatt_fwd", k, nnz, "att_fwd_kernel (hard)", stream);
 }
 
 extern "C" int mgcn_hatt_fwd_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -292,9 +206,10 @@ extern "C" int mgcn_hatt_fwd_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_
                                   float temperature, const float *alpha_in, const float *mask,
                                   const uint16_t *Hp, int64_t ldh, uint16_t *Y, int64_t ldy,
                                   float *alpha, void *stream) {
-  return hatt_fwd<uint16_t>("mgcn_hatt_fwd_bf16", n_rows, nnz, H, C, rowptr, col, s_row, s_col,
-                            act, noise, temperature, alpha_in, mask, Hp, ldh, Y, ldy, alpha,
-                            stream);
+  HardFwdArgsT<uint16_t> k{{n_rows, H, C, act, rowptr, col, s_row, s_col, alpha_in, mask, Hp, ldh,
+                            Y, ldy, alpha},
+                           noise, temperature};
+  return fwd<true>("mgcn_hatt_fwd_bf16", k, nnz, "att_fwd_kernel (hard)", stream);
 }
 
 extern "C" int mgcn_hatt_edge_softmax(int64_t n_rows, int64_t nnz, int32_t H,
@@ -302,18 +217,10 @@ extern "C" int mgcn_hatt_edge_softmax(int64_t n_rows, int64_t nnz, int32_t H,
                                       const float *s_row, const float *s_col, int act,
                                       const float *noise, float temperature, float *alpha,
                                       void *stream) {
-  clear_error();
-  ATT_REQUIRE_SHAPE("mgcn_hatt_edge_softmax", n_rows, nnz, H, 1);
-  ATT_ACT_OK("mgcn_hatt_edge_softmax", act);
-  HATT_TEMPERATURE_OK("mgcn_hatt_edge_softmax", temperature);
-  if (n_rows == 0 || nnz == 0) return MGCN_OK;
-  MGCN_REQUIRE(rowptr && col && s_row && s_col && alpha, "mgcn_hatt_edge_softmax: null array");
   HardFwdArgs k{{n_rows, H, 1, act, rowptr, col, s_row, s_col, nullptr, nullptr, nullptr, 0,
                  nullptr, 0, alpha},
                 noise, temperature};
-  hipLaunchKernelGGL((att_fwd_kernel<1, false, HardFwdArgs>), dim3(att_grid(n_rows)),
-                     dim3(kAttThreads), 0, as_stream(stream), k);
-  return check_launch("att_fwd_kernel (hard softmax)");
+  return fwd<false>("mgcn_hatt_edge_softmax", k, nnz, "att_fwd_kernel (hard softmax)", stream);
 }
 
 extern "C" int mgcn_hatt_bwd_dst(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -322,9 +229,10 @@ extern "C" int mgcn_hatt_bwd_dst(int64_t n_rows, int64_t nnz, int32_t H, int32_t
                                  const float *mask, const float *s_row, const float *s_col,
                                  int act, int softmax, float temperature, float *dz,
                                  float *ds_row, void *stream) {
-  return hatt_bwd_dst<float>("mgcn_hatt_bwd_dst", n_rows, nnz, H, C, rowptr, col, Hp, ldh, dY,
-                             lddy, alpha, mask, s_row, s_col, act, softmax, temperature, dz,
-                             ds_row, stream);
+  HardBwdDstArgs k{{n_rows, H, C, act, softmax ? 1 : 0, rowptr, col, Hp, ldh, dY, lddy,
+                    alpha, mask, s_row, s_col, dz, ds_row},
+                   temperature};
+  return bwd_dst("mgcn_hatt_bwd_dst", k, nnz, "att_bwd_dst_kernel (hard)", stream);
 }
 
 extern "C" int mgcn_hatt_bwd_dst_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -334,9 +242,10 @@ extern "C" int mgcn_hatt_bwd_dst_bf16(int64_t n_rows, int64_t nnz, int32_t H, in
                                       const float *s_row, const float *s_col, int act,
                                       int softmax, float temperature, float *dz, float *ds_row,
                                       void *stream) {
-  return hatt_bwd_dst<uint16_t>("mgcn_hatt_bwd_dst_bf16", n_rows, nnz, H, C, rowptr, col, Hp, ldh,
-                                dY, lddy, alpha, mask, s_row, s_col, act, softmax, temperature,
-                                dz, ds_row, stream);
+  HardBwdDstArgsT<uint16_t> k{{n_rows, H, C, act, softmax ? 1 : 0, rowptr, col, Hp, ldh, dY, lddy,
+                               alpha, mask, s_row, s_col, dz, ds_row},
+                              temperature};
+  return bwd_dst("mgcn_hatt_bwd_dst_bf16", k, nnz, "att_bwd_dst_kernel (hard)", stream);
 }
 
 extern "C" int mgcn_hatt_bwd_src(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -349,7 +258,7 @@ extern "C" int mgcn_hatt_bwd_src(int64_t n_rows, int64_t nnz, int32_t H, int32_t
   HardBwdSrcArgs k{{n_rows, H, C, act, softmax ? 1 : 0, rowptr_t, col_t, slot_map, dY, lddy,
                     alpha, mask, dz, s_row, s_col, a, ds_dst, ds_src, dHp, lddh},
                    temperature};
-  return hatt_bwd_src("mgcn_hatt_bwd_src", k, nnz, stream);
+  return bwd_src("mgcn_hatt_bwd_src", k, nnz, "att_bwd_src_kernel (hard)", stream);
 }
 
 extern "C" int mgcn_hatt_bwd_src_bf16(int64_t n_rows, int64_t nnz, int32_t H, int32_t C,
@@ -365,7 +274,7 @@ extern "C" int mgcn_hatt_bwd_src_bf16(int64_t n_rows, int64_t nnz, int32_t H, in
                                       ds_dst, ds_src, dHp, lddh},
                                      dHp_f32},
                                     temperature};
-  return hatt_bwd_src("mgcn_hatt_bwd_src_bf16", k, nnz, stream);
+  return bwd_src("mgcn_hatt_bwd_src_bf16", k, nnz, "att_bwd_src_kernel (hard)", stream);
 }
 
 extern "C" int mgcn_hatt_select(int64_t n_rows, int64_t nnz, int32_t H, const int64_t *rowptr,

@@ -215,6 +215,25 @@ __device__ unsigned long long g_hprof[3][256][2];
 struct HeavyNoEpi {
   __device__ __forceinline__ float operator()(int, float v) const { return v; }
 };
+
+// The launch shape of heavy_row_block for HB threads: feature chunk FC, edge
+// batch BE and the dynamic LDS they take out of `lds_budget` bytes -- 2
+// product buffers of FC x (BE + 4) floats + a 3-slot ring of 4 x BE words.  A
+// small budget still gets one 16-edge batch (<= 21 KB).
+struct HeavyShape {
+  int FC, BE;
+  size_t lds;
+};
+inline HeavyShape heavy_shape(int F, int VEC, int HB, int lds_budget) {
+  int FC = F < 128 ? F : 128;
+  FC = (FC + VEC - 1) / VEC * VEC;
+  const int producers = HB - 64 * ((FC + 63) / 64);
+  int BE = (lds_budget / 4 - 8 * FC) / (2 * FC + 12);
+  if (BE > 4 * producers) BE = 4 * producers;  // kEpt metadata entries per producer
+  BE &= ~15;
+  if (BE < 16) BE = 16;
+  return {FC, BE, sizeof(float) * ((size_t)2 * FC * (BE + 4) + (size_t)12 * BE)};
+}
 template <int VEC, int MODE, int HB, int Q = 0, typename T = float, class Epi = HeavyNoEpi>
 __device__ __forceinline__ void heavy_row_block(const SpmmArgs &a, int FC, int BE, int64_t hidx,
                                                 float *__restrict__ smem, Epi epi = Epi{}) {

@@ -149,6 +149,22 @@ inline int check_launch(const char *what) {
     }                                 \
   } while (0)
 
+// Let `kernel` take up to max_bytes of dynamic LDS on the current device.  The
+// attribute is per device: attr_set (a static of the calling launcher, so one
+// per kernel instantiation) holds one bit per device id; racing threads at
+// worst both set it.
+inline int allow_lds(const void *kernel, std::atomic<uint64_t> &attr_set, int max_bytes) {
+  int dev = 0;
+  MGCN_HIP_TRY(hipGetDevice(&dev));
+  const uint64_t bit = uint64_t(1) << (dev & 63);
+  if (!(attr_set.load(std::memory_order_acquire) & bit)) {
+    MGCN_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     max_bytes));
+    attr_set.fetch_or(bit, std::memory_order_release);
+  }
+  return MGCN_OK;
+}
+
 // MGCN_EWORKSPACE ("<who>: workspace <given> < <need>") unless `workspace` holds `need` bytes
 inline int require_workspace(const char *who, const void *workspace, size_t bytes, size_t need) {
   if (workspace != nullptr && bytes >= need) return MGCN_OK;

@@ -507,20 +507,13 @@ int launch_g(const SpmmArgs &a, hipStream_t stream) {
 }
 
 template <int VEC, int MODE, int HB, int Q>
-int launch_heavy_q(const SpmmArgs &a, int64_t n, int FC, int BE, size_t lds, hipStream_t stream) {
-  // the 160 KB dynamic-LDS attribute is per device: one bit per device id,
-  // per instantiation (VEC, MODE, HB, Q); racing threads at worst both set it
-  static std::atomic<uint64_t> attr_set{0};
-  int dev = 0;
-  MGCN_HIP_TRY(hipGetDevice(&dev));
-  const uint64_t bit = uint64_t(1) << (dev & 63);
-  if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-    MGCN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&spmm_heavy_kernel<VEC, MODE, HB, Q>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set.fetch_or(bit, std::memory_order_release);
-  }
-  hipLaunchKernelGGL((spmm_heavy_kernel<VEC, MODE, HB, Q>), dim3((unsigned)n), dim3(HB), lds, stream,
-                     a, FC, BE);
+int launch_heavy_q(const SpmmArgs &a, int64_t n, const HeavyShape &h, hipStream_t stream) {
+  static std::atomic<uint64_t> attr_set{0};  // per instantiation (VEC, MODE, HB, Q)
+  if (int rc = allow_lds(reinterpret_cast<const void *>(&spmm_heavy_kernel<VEC, MODE, HB, Q>),
+                         attr_set, 160 * 1024))
+    return rc;
+  hipLaunchKernelGGL((spmm_heavy_kernel<VEC, MODE, HB, Q>), dim3((unsigned)n), dim3(HB), h.lds,
+                     stream, a, h.FC, h.BE);
   return check_launch("spmm_heavy_kernel");
 }
 
@@ -529,21 +522,13 @@ int launch_heavy_hb(SpmmArgs a, const int32_t *rows, int64_t n, int lds_budget,
                     hipStream_t stream) {
   if (n <= 0) return MGCN_OK;
   a.heavy_rows = rows;
-  int FC = a.F < 128 ? a.F : 128;
-  FC = (FC + VEC - 1) / VEC * VEC;
-  const int producers = HB - 64 * ((FC + 63) / 64);
-  // 2 product buffers of FC x (BE + 4) floats + a 3-slot ring of 4 x BE words
-  int BE = (lds_budget / 4 - 8 * FC) / (2 * FC + 12);
-  if (BE > 4 * producers) BE = 4 * producers;  // kEpt metadata entries per producer
-  BE &= ~15;
-  if (BE < 16) BE = 16;  // a small budget still gets one 16-edge batch (<= 21 KB)
-  const size_t lds = sizeof(float) * ((size_t)2 * FC * (BE + 4) + (size_t)12 * BE);
+  const HeavyShape h = heavy_shape(a.F, VEC, HB, lds_budget);
   // narrow rows (FC <= 32, config 3's F = 32) in the 256-thread workgroups:
   // one edge quad in flight per producer (84 VGPRs instead of 172-188, so
   // LDS, not registers, sets the workgroups per CU): 2.77 -> 2.67 ms/step
   if constexpr (HB == 256)
-    if (FC <= 32 && g_opt.heavy_mid_q1) return launch_heavy_q<VEC, MODE, HB, 1>(a, n, FC, BE, lds, stream);
-  return launch_heavy_q<VEC, MODE, HB, 0>(a, n, FC, BE, lds, stream);
+    if (h.FC <= 32 && g_opt.heavy_mid_q1) return launch_heavy_q<VEC, MODE, HB, 1>(a, n, h, stream);
+  return launch_heavy_q<VEC, MODE, HB, 0>(a, n, h, stream);
 }
 
 template <int VEC, int MODE>

@@ -347,40 +347,25 @@ __global__ __launch_bounds__(HB) void spmm_bf16_heavy_kernel(const SpmmArgs a, i
 }
 
 template <int MODE, int HB, int Q>
-int launch_heavy_q(const SpmmArgs &a, int64_t n, int FC, int BE, size_t lds, hipStream_t stream) {
-  // the 160 KB dynamic-LDS attribute is per device: one bit per device id,
-  // per instantiation; racing threads at worst both set it
-  static std::atomic<uint64_t> attr_set{0};
-  int dev = 0;
-  MGCN_HIP_TRY(hipGetDevice(&dev));
-  const uint64_t bit = uint64_t(1) << (dev & 63);
-  if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-    MGCN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&spmm_bf16_heavy_kernel<MODE, HB, Q>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kGiantLds));
-    attr_set.fetch_or(bit, std::memory_order_release);
-  }
-  hipLaunchKernelGGL((spmm_bf16_heavy_kernel<MODE, HB, Q>), dim3((unsigned)n), dim3(HB), lds, stream,
-                     a, FC, BE);
+int launch_heavy_q(const SpmmArgs &a, int64_t n, const HeavyShape &h, hipStream_t stream) {
+  static std::atomic<uint64_t> attr_set{0};  // per instantiation
+  if (int rc = allow_lds(reinterpret_cast<const void *>(&spmm_bf16_heavy_kernel<MODE, HB, Q>),
+                         attr_set, kGiantLds))
+    return rc;
+  hipLaunchKernelGGL((spmm_bf16_heavy_kernel<MODE, HB, Q>), dim3((unsigned)n), dim3(HB), h.lds,
+                     stream, a, h.FC, h.BE);
   return check_launch("spmm_bf16_heavy_kernel");
 }
 
-// the batch size and LDS block of spmm.hip's launch_heavy_hb
 template <int MODE, int HB>
 int launch_heavy_hb(SpmmArgs a, const int32_t *rows, int64_t n, int lds_budget,
                     hipStream_t stream) {
   if (n <= 0) return MGCN_OK;
   a.heavy_rows = rows;
-  int FC = a.F < 128 ? a.F : 128;  // F % 8 == 0: a multiple of kHeavyVec
-  const int producers = HB - 64 * ((FC + 63) / 64);
-  // 2 product buffers of FC x (BE + 4) floats + a 3-slot ring of 4 x BE words
-  int BE = (lds_budget / 4 - 8 * FC) / (2 * FC + 12);
-  if (BE > 4 * producers) BE = 4 * producers;  // kEpt metadata entries per producer
-  BE &= ~15;
-  if (BE < 16) BE = 16;
-  const size_t lds = sizeof(float) * ((size_t)2 * FC * (BE + 4) + (size_t)12 * BE);
+  const HeavyShape h = heavy_shape(a.F, kHeavyVec, HB, lds_budget);  // F % 8 == 0: FC = min(F, 128)
   if constexpr (HB == 256)
-    if (FC <= 32) return launch_heavy_q<MODE, HB, 1>(a, n, FC, BE, lds, stream);
-  return launch_heavy_q<MODE, HB, 0>(a, n, FC, BE, lds, stream);
+    if (h.FC <= 32) return launch_heavy_q<MODE, HB, 1>(a, n, h, stream);
+  return launch_heavy_q<MODE, HB, 0>(a, n, h, stream);
 }
 
 template <int MODE>

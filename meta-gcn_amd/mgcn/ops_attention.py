@@ -124,29 +124,89 @@ def _datt(ds_src, ds_dst, Hp, H: int, C: int):
     return torch.cat([full[0, hh, hh], full[1, hh, hh]], dim=1)  # [H, 2C]
 
 
-def _bwd_src_fold(lib, hard_T, bf16, inn, plan, H, C, act, dY, alpha, mask, dz, s_src, s_dst, att,
-                  ds_dst, ds_src, st):
-    """mgcn_(h)att_bwd_src and, for 'out', mgcn_att_dst_fold: dHp in the row
-    dtype.  bf16 rows under 'out' hand the unrounded fp32 row from the first
-    launch to the second through a scratch [N, H C], so dHp is rounded once."""
-    dev = dY.device
-    N, nnz, HC = plan.num_nodes, plan.nnz, H * C
+def _train_forward(ctx, Hp, att, mask, noise, T, plan: GraphPlan, H: int, act: int, att_dir: str):
+    """The forward of :class:`_AttentionAggregate` (``noise`` and ``T`` None:
+    the mgcn_att_* entries) and of :class:`_HardAttentionTrain` (the
+    mgcn_hatt_* entries, which take ``noise, T`` after ``act``)."""
+    hard = T is not None
+    fwd_name, softmax_name = ("hatt_fwd", "hatt_edge_softmax") if hard else ("att_fwd",
+                                                                             "edge_softmax")
+    noise_T = (L.ptr(noise), T) if hard else ()
+    lib = L.load()
+    dev = Hp.device
+    N, HC = Hp.shape
+    C = HC // H
+    nnz = plan.nnz
+    st = L.stream_of(dev)
+    bf = Hp.dtype == BF16
+    att = att.detach().contiguous()
+    s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+    s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
+    Y = torch.empty(N, HC, dtype=Hp.dtype, device=dev)
+    alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
     fwd, bwd = plan.fwd, plan.bwd
+    _row_launch(lib, "att_scores", bf, dev, N, None,
+                N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
+    if att_dir == 'in' or nnz == 0:
+        _view_launch(lib, fwd_name, bf, dev, N, fwd, nnz, H, True,
+                     N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst),
+                     L.ptr(s_src), act, *noise_T, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0),
+                     L.ptr(Y), HC, L.ptr(alpha), st)
+    else:
+        a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+        _view_launch(lib, softmax_name, False, dev, N, bwd, nnz, H, False,
+                     N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src),
+                     L.ptr(s_dst), act, *noise_T, L.ptr(a_bwd), st, bf16_rows=bf)
+        alpha[plan.slot_map()[:nnz].long()] = a_bwd
+        _view_launch(lib, fwd_name, bf, dev, N, fwd, nnz, H, True,
+                     N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act,
+                     *((None, T) if hard else ()), L.ptr(alpha), L.ptr(mask), L.ptr(Hp),
+                     Hp.stride(0), L.ptr(Y), HC, None, st)
+    ctx.plan, ctx.H, ctx.act, ctx.att_dir, ctx.T = plan, H, act, att_dir, T
+    ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
+    ctx.mark_non_differentiable(alpha)
+    return Y, alpha
+
+
+def _train_backward(ctx, dY):
+    """``(dHp, datt)`` of either training function (``ctx.T`` None: soft):
+    mgcn_(h)att_bwd_dst, mgcn_(h)att_bwd_src and, for 'out', mgcn_att_dst_fold.
+    bf16 rows under 'out' hand the unrounded fp32 row from bwd_src to the fold
+    through a scratch [N, H C], so dHp is rounded once."""
+    Hp, att, alpha, mask, s_src, s_dst = ctx.saved_tensors
+    plan, H, act, T = ctx.plan, ctx.H, ctx.act, ctx.T
+    pre, temp = ("att_", ()) if T is None else ("hatt_", (T,))
+    lib = L.load()
+    dev = Hp.device
+    N, HC = Hp.shape
+    C = HC // H
+    nnz = plan.nnz
+    st = L.stream_of(dev)
+    bf = Hp.dtype == BF16
+    dY = _grad_rows(dY, Hp.dtype)
+    fwd, bwd = plan.fwd, plan.bwd
+    dz = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+    ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
+    ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
+    inn = ctx.att_dir == 'in'
+    _view_launch(lib, pre + "bwd_dst", bf, dev, N, fwd, nnz, H, False,
+                 N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
+                 L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst),
+                 L.ptr(s_src), act, int(inn), *temp, L.ptr(dz), L.ptr(ds_dst), st)
     slot = plan.slot_map() if nnz else None
     dHp = torch.empty(N, HC, dtype=dY.dtype, device=dev)
-    park = torch.empty(N, HC, dtype=torch.float32, device=dev) if bf16 and not inn else None
-    _view_launch(lib, "att_bwd_src" if hard_T is None else "hatt_bwd_src", bf16, dev, N, bwd,
-                 nnz, H, True,
+    park = torch.empty(N, HC, dtype=torch.float32, device=dev) if bf and not inn else None
+    _view_launch(lib, pre + "bwd_src", bf, dev, N, bwd, nnz, H, True,
                  N, nnz, H, C, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(slot), L.ptr(dY),
                  dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(dz), L.ptr(s_src), L.ptr(s_dst),
-                 act, int(not inn), *(() if hard_T is None else (hard_T,)), L.ptr(att),
-                 L.ptr(ds_dst) if inn else None, L.ptr(ds_src), L.ptr(dHp), HC,
-                 *((L.ptr(park),) if bf16 else ()), st)
+                 act, int(not inn), *temp, L.ptr(att), L.ptr(ds_dst) if inn else None,
+                 L.ptr(ds_src), L.ptr(dHp), HC, *((L.ptr(park),) if bf else ()), st)
     if not inn:
-        _row_launch(lib, "att_dst_fold", bf16, dev, N, fwd.edges,
+        _row_launch(lib, "att_dst_fold", bf, dev, N, fwd.edges,
                     N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(dz), L.ptr(att), L.ptr(ds_dst),
-                    *((L.ptr(park),) if bf16 else ()), L.ptr(dHp), HC, st)
-    return dHp
+                    *((L.ptr(park),) if bf else ()), L.ptr(dHp), HC, st)
+    datt = _datt(ds_src, ds_dst, Hp, H, C) if ctx.needs_input_grad[1] else None
+    return dHp, datt
 
 
 class _AttentionAggregate(torch.autograd.Function):
@@ -166,67 +226,57 @@ class _AttentionAggregate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Hp, att, mask, plan: GraphPlan, H: int, act: int, att_dir: str):
-        lib = L.load()
-        dev = Hp.device
-        N, HC = Hp.shape
-        C = HC // H
-        nnz = plan.nnz
-        st = L.stream_of(dev)
-        bf = Hp.dtype == BF16
-        att = att.detach().contiguous()
-        s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        Y = torch.empty(N, HC, dtype=Hp.dtype, device=dev)
-        alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-        fwd, bwd = plan.fwd, plan.bwd
-        _row_launch(lib, "att_scores", bf, dev, N, None,
-                    N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
-        if att_dir == 'in' or nnz == 0:
-            _view_launch(lib, "att_fwd", bf, dev, N, fwd, nnz, H, True,
-                         N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst),
-                         L.ptr(s_src), act, None, L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y),
-                         HC, L.ptr(alpha), st)
-        else:
-            a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-            _view_launch(lib, "edge_softmax", False, dev, N, bwd, nnz, H, False,
-                         N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src),
-                         L.ptr(s_dst), act,
-                         L.ptr(a_bwd), st, bf16_rows=bf)
-            alpha[plan.slot_map()[:nnz].long()] = a_bwd
-            _view_launch(lib, "att_fwd", bf, dev, N, fwd, nnz, H, True,
-                         N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act,
-                         L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None,
-                         st)
-        ctx.plan, ctx.H, ctx.act, ctx.att_dir = plan, H, act, att_dir
-        ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
-        ctx.mark_non_differentiable(alpha)
-        return Y, alpha
+        return _train_forward(ctx, Hp, att, mask, None, None, plan, H, act, att_dir)
 
     @staticmethod
     def backward(ctx, dY, _dalpha):
-        Hp, att, alpha, mask, s_src, s_dst = ctx.saved_tensors
-        plan, H, act = ctx.plan, ctx.H, ctx.act
-        lib = L.load()
-        dev = Hp.device
-        N, HC = Hp.shape
-        C = HC // H
-        nnz = plan.nnz
-        st = L.stream_of(dev)
-        bf = Hp.dtype == BF16
-        dY = _grad_rows(dY, Hp.dtype)
-        fwd = plan.fwd
-        dz = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-        ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        inn = ctx.att_dir == 'in'
-        _view_launch(lib, "att_bwd_dst", bf, dev, N, fwd, nnz, H, False,
-                     N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
-                     L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst),
-                     L.ptr(s_src), act, int(inn), L.ptr(dz), L.ptr(ds_dst), st)
-        dHp = _bwd_src_fold(lib, None, bf, inn, plan, H, C, act, dY, alpha, mask, dz, s_src, s_dst,
-                            att, ds_dst, ds_src, st)
-        datt = _datt(ds_src, ds_dst, Hp, H, C) if ctx.needs_input_grad[1] else None
-        return dHp, datt, None, None, None, None, None
+        return (*_train_backward(ctx, dY), None, None, None, None, None)
+
+
+def _check_args(who: str, Hp, att_weight, plan: GraphPlan, nheads: int, act: str, att_dir: str,
+                *others):
+    """The argument checks :func:`attention_aggregate` and
+    :func:`hard_attention_aggregate` (``who``) share; ``others``: further
+    tensors that must live on Hp's device.  Returns the rows [N, H C], the
+    fp32 attention vector [H, 2C] and H."""
+    _require_row_dtype(Hp, "Hp")
+    L.require_device(Hp, att_weight, plan.fwd.rowptr, *others)
+    if act not in L.ATT_ACT_CODES:
+        raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
+    if att_dir not in ('in', 'out'):
+        raise ValueError(f"att_dir must be 'in' or 'out', got {att_dir!r}")
+    H = int(nheads)
+    Hp2 = _rows(Hp.reshape(Hp.size(0), -1), "Hp")
+    if Hp2.size(0) != plan.num_nodes:
+        raise ValueError(f"Hp has {Hp2.size(0)} rows, graph has {plan.num_nodes} nodes")
+    HC = Hp2.size(1)
+    if H < 1 or HC % H:
+        raise ValueError(f"Hp width {HC} is not a multiple of nheads = {H}")
+    C = HC // H
+    att2 = _att_f32(att_weight, H, C)
+    if not (1 <= H <= 16 and HC <= 1024 and plan.nnz * H < 2 ** 31):
+        raise L.MgcnError(f"{who}: unsupported shape (H = {H}, C = {C}, nnz = "
+                          f"{plan.nnz}): need 1 <= H <= 16, H C <= 1024, nnz H < 2^31")
+    return Hp2, att2, H
+
+
+def _slot_mask(edge_mask, plan: GraphPlan, H: int):
+    """``edge_mask`` [E, H] (COO order; None stays None) as fp32 in fwd slot order."""
+    if edge_mask is None:
+        return None
+    if tuple(edge_mask.shape) != (plan.nnz, H):
+        raise ValueError(f"edge_mask must be [{plan.nnz}, {H}] in COO order, got "
+                         f"{tuple(edge_mask.shape)}")
+    return edge_mask.detach().to(torch.float32)[plan.fwd.eid.long()].contiguous()
+
+
+def _alpha_coo(alpha, mask, plan: GraphPlan):
+    """alpha' = alpha * mask, detached, carried from fwd slot order to COO order."""
+    alpha = alpha.detach()
+    alpha_coo = torch.empty_like(alpha)
+    if plan.nnz:
+        alpha_coo[plan.fwd.eid.long()] = alpha * mask if mask is not None else alpha
+    return alpha_coo
 
 
 def attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphPlan, nheads: int,
@@ -249,36 +299,11 @@ def attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphP
     bfloat16 ``Hp`` the feature rows stay bf16 through every kernel and Y and
     the gradient of Hp are bf16; alpha stays fp32.  ``att_weight`` may be
     float32 or bfloat16 with either (its gradient has its dtype)."""
-    _require_row_dtype(Hp, "Hp")
-    L.require_device(Hp, att_weight, plan.fwd.rowptr, edge_mask)
-    if act not in L.ATT_ACT_CODES:
-        raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
-    if att_dir not in ('in', 'out'):
-        raise ValueError(f"att_dir must be 'in' or 'out', got {att_dir!r}")
-    H = int(nheads)
-    Hp2 = _rows(Hp.reshape(Hp.size(0), -1), "Hp")
-    if Hp2.size(0) != plan.num_nodes:
-        raise ValueError(f"Hp has {Hp2.size(0)} rows, graph has {plan.num_nodes} nodes")
-    HC = Hp2.size(1)
-    if H < 1 or HC % H:
-        raise ValueError(f"Hp width {HC} is not a multiple of nheads = {H}")
-    C = HC // H
-    att2 = _att_f32(att_weight, H, C)
-    if not (1 <= H <= 16 and HC <= 1024 and plan.nnz * H < 2 ** 31):
-        raise L.MgcnError(f"attention_aggregate: unsupported shape (H = {H}, C = {C}, nnz = "
-                          f"{plan.nnz}): need 1 <= H <= 16, H C <= 1024, nnz H < 2^31")
-    mask = None
-    if edge_mask is not None:
-        if tuple(edge_mask.shape) != (plan.nnz, H):
-            raise ValueError(f"edge_mask must be [{plan.nnz}, {H}] in COO order, got "
-                             f"{tuple(edge_mask.shape)}")
-        mask = edge_mask.detach().to(torch.float32)[plan.fwd.eid.long()].contiguous()
+    Hp2, att2, H = _check_args("attention_aggregate", Hp, att_weight, plan, nheads, act, att_dir,
+                               edge_mask)
+    mask = _slot_mask(edge_mask, plan, H)
     Y, alpha = _AttentionAggregate.apply(Hp2, att2, mask, plan, H, L.ATT_ACT_CODES[act], att_dir)
-    alpha = alpha.detach()
-    alpha_coo = torch.empty_like(alpha)
-    if plan.nnz:
-        alpha_coo[plan.fwd.eid.long()] = alpha * mask if mask is not None else alpha
-    return Y, alpha_coo
+    return Y, _alpha_coo(alpha, mask, plan)
 
 
 # ---------------------------------------------------------- hard attention
@@ -293,67 +318,11 @@ class _HardAttentionTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Hp, att, mask, noise, plan: GraphPlan, H: int, act: int, att_dir: str,
                 T: float):
-        lib = L.load()
-        dev = Hp.device
-        N, HC = Hp.shape
-        C = HC // H
-        nnz = plan.nnz
-        st = L.stream_of(dev)
-        bf = Hp.dtype == BF16
-        att = att.detach().contiguous()
-        s_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        s_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        Y = torch.empty(N, HC, dtype=Hp.dtype, device=dev)
-        alpha = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-        fwd, bwd = plan.fwd, plan.bwd
-        _row_launch(lib, "att_scores", bf, dev, N, None,
-                    N, H, C, L.ptr(Hp), Hp.stride(0), L.ptr(att), L.ptr(s_src), L.ptr(s_dst), st)
-        if att_dir == 'in' or nnz == 0:
-            _view_launch(lib, "hatt_fwd", bf, dev, N, fwd, nnz, H, True,
-                         N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(s_dst),
-                         L.ptr(s_src), act, L.ptr(noise), T, None, L.ptr(mask), L.ptr(Hp),
-                         Hp.stride(0), L.ptr(Y), HC, L.ptr(alpha), st)
-        else:
-            a_bwd = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-            _view_launch(lib, "hatt_edge_softmax", False, dev, N, bwd, nnz, H, False,
-                         N, nnz, H, L.ptr(bwd.rowptr), L.ptr(bwd.col), L.ptr(s_src),
-                         L.ptr(s_dst), act,
-                         L.ptr(noise), T, L.ptr(a_bwd), st, bf16_rows=bf)
-            alpha[plan.slot_map()[:nnz].long()] = a_bwd
-            _view_launch(lib, "hatt_fwd", bf, dev, N, fwd, nnz, H, True,
-                         N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), None, None, act, None, T,
-                         L.ptr(alpha), L.ptr(mask), L.ptr(Hp), Hp.stride(0), L.ptr(Y), HC, None,
-                         st)
-        ctx.plan, ctx.H, ctx.act, ctx.att_dir, ctx.T = plan, H, act, att_dir, T
-        ctx.save_for_backward(Hp, att, alpha, mask, s_src, s_dst)
-        ctx.mark_non_differentiable(alpha)
-        return Y, alpha
+        return _train_forward(ctx, Hp, att, mask, noise, T, plan, H, act, att_dir)
 
     @staticmethod
     def backward(ctx, dY, _dalpha):
-        Hp, att, alpha, mask, s_src, s_dst = ctx.saved_tensors
-        plan, H, act, T = ctx.plan, ctx.H, ctx.act, ctx.T
-        lib = L.load()
-        dev = Hp.device
-        N, HC = Hp.shape
-        C = HC // H
-        nnz = plan.nnz
-        st = L.stream_of(dev)
-        bf = Hp.dtype == BF16
-        dY = _grad_rows(dY, Hp.dtype)
-        fwd = plan.fwd
-        dz = torch.empty(nnz, H, dtype=torch.float32, device=dev)
-        ds_src = torch.empty(N, H, dtype=torch.float32, device=dev)
-        ds_dst = torch.empty(N, H, dtype=torch.float32, device=dev)
-        inn = ctx.att_dir == 'in'
-        _view_launch(lib, "hatt_bwd_dst", bf, dev, N, fwd, nnz, H, False,
-                     N, nnz, H, C, L.ptr(fwd.rowptr), L.ptr(fwd.col), L.ptr(Hp), Hp.stride(0),
-                     L.ptr(dY), dY.stride(0), L.ptr(alpha), L.ptr(mask), L.ptr(s_dst),
-                     L.ptr(s_src), act, int(inn), T, L.ptr(dz), L.ptr(ds_dst), st)
-        dHp = _bwd_src_fold(lib, T, bf, inn, plan, H, C, act, dY, alpha, mask, dz, s_src, s_dst,
-                            att, ds_dst, ds_src, st)
-        datt = _datt(ds_src, ds_dst, Hp, H, C) if ctx.needs_input_grad[1] else None
-        return dHp, datt, None, None, None, None, None, None, None
+        return (*_train_backward(ctx, dY), None, None, None, None, None, None, None)
 
 
 class _HardAttentionEval(torch.autograd.Function):
@@ -459,24 +428,8 @@ def hard_attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: G
     Returns ``(Y, alpha_coo)``: Y [N, H * C] and the coefficients that weighted
     the messages, [E, H] in COO order, detached.  ``Hp`` float32 or bfloat16 as
     for :func:`attention_aggregate`."""
-    _require_row_dtype(Hp, "Hp")
-    L.require_device(Hp, att_weight, plan.fwd.rowptr, edge_mask, noise)
-    if act not in L.ATT_ACT_CODES:
-        raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
-    if att_dir not in ('in', 'out'):
-        raise ValueError(f"att_dir must be 'in' or 'out', got {att_dir!r}")
-    H = int(nheads)
-    Hp2 = _rows(Hp.reshape(Hp.size(0), -1), "Hp")
-    if Hp2.size(0) != plan.num_nodes:
-        raise ValueError(f"Hp has {Hp2.size(0)} rows, graph has {plan.num_nodes} nodes")
-    HC = Hp2.size(1)
-    if H < 1 or HC % H:
-        raise ValueError(f"Hp width {HC} is not a multiple of nheads = {H}")
-    C = HC // H
-    att2 = _att_f32(att_weight, H, C)
-    if not (1 <= H <= 16 and HC <= 1024 and plan.nnz * H < 2 ** 31):
-        raise L.MgcnError(f"hard_attention_aggregate: unsupported shape (H = {H}, C = {C}, nnz = "
-                          f"{plan.nnz}): need 1 <= H <= 16, H C <= 1024, nnz H < 2^31")
+    Hp2, att2, H = _check_args("hard_attention_aggregate", Hp, att_weight, plan, nheads, act,
+                               att_dir, edge_mask, noise)
     T = float(temperature)
     if training and not T > 0:
         raise ValueError(f"temperature must be positive, got {temperature!r}")
@@ -489,18 +442,10 @@ def hard_attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: G
         noise = noise.detach().to(torch.float32)[walked.eid.long()].contiguous()
     mask = None
     if training:
-        if edge_mask is not None:
-            if tuple(edge_mask.shape) != (plan.nnz, H):
-                raise ValueError(f"edge_mask must be [{plan.nnz}, {H}] in COO order, got "
-                                 f"{tuple(edge_mask.shape)}")
-            mask = edge_mask.detach().to(torch.float32)[plan.fwd.eid.long()].contiguous()
+        mask = _slot_mask(edge_mask, plan, H)
         Y, alpha = _HardAttentionTrain.apply(Hp2, att2, mask, noise, plan, H,
                                              L.ATT_ACT_CODES[act], att_dir, T)
     else:
         Y, alpha = _HardAttentionEval.apply(Hp2, att2.detach(), noise, plan, H,
                                             L.ATT_ACT_CODES[act], att_dir)
-    alpha = alpha.detach()
-    alpha_coo = torch.empty_like(alpha)
-    if plan.nnz:
-        alpha_coo[plan.fwd.eid.long()] = alpha * mask if mask is not None else alpha
-    return Y, alpha_coo
+    return Y, _alpha_coo(alpha, mask, plan)
