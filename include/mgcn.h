@@ -1582,6 +1582,39 @@ int mgcn_csr_derive(
     int64_t *rowptr_out, int32_t *col_out, int32_t *eid_out,
     void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Seeded per-edge random fills (edge_noise.hip): the Gumbel noise of hard
+ * attention / VotePool and the attention dropout mask, written on the device
+ * directly in the slot order of a view.  A backward-compatible addition:
+ * MGCN_ABI_VERSION stays 22.
+ *
+ * out is [nnz, H], contiguous fp32.  Slot k belongs to COO edge e = eid[k]
+ * (eid NULL: e = k, COO order), and out[k, h] depends on (kind, seed, offset,
+ * e, h, p) alone: the fill of a view is the COO fill carried to its slots.
+ *
+ * u comes from Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl
+ * constants 0x9E3779B9 / 0xBB67AE85) under the key (seed & 0xffffffff,
+ * seed >> 32) and the counter (e, h / 4, offset & 0xffffffff, offset >> 32):
+ * output word h % 4 serves head h, u = float(word >> 8) * 2^-24 (exact, so
+ * 0 <= u <= 1 - 2^-24).
+ *   UNIFORM  u
+ *   GUMBEL   -logf(-logf(u + 1e-20f) + 1e-20f), the reference's fp32 operations
+ *            in its order (graph_hard_attention.py:12-20); finite for every u
+ *   DROPOUT  u >= p ? 1.0f / (1.0f - p) : 0.0f (one fp32 division): p == 0
+ *            gives 1 everywhere, p == 1 gives 0 everywhere
+ * p is read by DROPOUT alone.
+ *
+ * MGCN_EINVAL before any launch, out untouched: an unknown kind, nnz < 0,
+ * H outside 1 .. 16, nnz * H >= 2^31, DROPOUT with p outside [0, 1] or NaN,
+ * out NULL with nnz > 0.  nnz == 0 succeeds and launches nothing.  eid values
+ * are not checked (they are a plan's own, from mgcn_csr_build).
+ */
+#define MGCN_NOISE_UNIFORM 0
+#define MGCN_NOISE_GUMBEL 1
+#define MGCN_NOISE_DROPOUT 2
+int mgcn_edge_noise(int kind, uint64_t seed, uint64_t offset, int64_t nnz, int32_t H,
+                    const int32_t *eid, float p, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,12 +18,14 @@ from . import _lib
 from ._lib import MgcnError, check_device, load, set_option
 from .graph import (GraphPlan, adopt_plan, build_plan, clear_cache, drop_edges, plan_for,
                     set_derived_plans)
-from .ops import (aggregate, attention_aggregate, gate_aggregate, hard_attention_aggregate,
-                  multi_aggregate, scatter_, segment_mean)
+from .ops import (DeviceDropout, DeviceGumbel, aggregate, attention_aggregate, draw_edge_seed,
+                  edge_noise, gate_aggregate, hard_attention_aggregate, multi_aggregate,
+                  scatter_, segment_mean)
 
 __version__ = "0.1.0"
 
 __all__ = ["MgcnError", "check_device", "load", "set_option", "GraphPlan", "build_plan", "plan_for",
            "clear_cache", "aggregate", "attention_aggregate", "gate_aggregate",
            "multi_aggregate", "hard_attention_aggregate", "scatter_", "segment_mean", "_lib",
-           "adopt_plan", "drop_edges", "set_derived_plans"]
+           "adopt_plan", "drop_edges", "set_derived_plans", "edge_noise", "DeviceGumbel",
+           "DeviceDropout", "draw_edge_seed"]

@@ -22,6 +22,7 @@ REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
 NORM_NONE, NORM_SM, NORM_RW = 0, 1, 2
 MAX_FILL = -1e38
 ATT_ACT_CODES = {"none": 0, "lrelu": 1, "relu": 2}
+NOISE_UNIFORM, NOISE_GUMBEL, NOISE_DROPOUT = 0, 1, 2  # mgcn_edge_noise kinds
 
 REDUCE_CODES = {"add": REDUCE_SUM, "sum": REDUCE_SUM, "mean": REDUCE_MEAN, "max": REDUCE_MAX}
 NORM_CODES = {None: NORM_NONE, "sm": NORM_SM, "rw": NORM_RW}
@@ -32,6 +33,7 @@ _i32 = ctypes.c_int32
 _int = ctypes.c_int
 _sz = ctypes.c_size_t
 _f32 = ctypes.c_float
+_u64 = ctypes.c_uint64
 
 MULTI_MAX_K = 8
 COMBINE_CODES = {"add": 0, "mean": 1, "cat": 2}
@@ -252,6 +254,7 @@ SIGNATURES = {
     "mgcn_csr_derive_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "mgcn_csr_derive": (_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp,
                                _vp, _vp, _vp, _sz, _vp]),
+    "mgcn_edge_noise": (_int, [_int, _u64, _u64, _i64, _i32, _vp, _f32, _vp, _vp]),
 }
 
 class PackedTableC(ctypes.Structure):

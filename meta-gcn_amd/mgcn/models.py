@@ -37,6 +37,7 @@ from .ops import (aggregate_plan, attention_aggregate, gcn_layer, gcn_stack, lin
                   multi_kernel_reason,
                   residual_gcn_layer, residual_layer_supported, residual_stack,  # noqa: F401
                   scatter_)
+from .ops_noise import DeviceDropout, DeviceGumbel, draw_edge_seed
 
 
 # --------------------------------------------------------------- inits (PyG)
@@ -361,6 +362,17 @@ class NodeModelGatedAdditive(NodeModelAdditive):
 
 
 # ------------------------------------------------------ graph_attention.py
+def _edge_rng(edge_rng):
+    """The ``edge_rng`` keyword of the attention modules: 'torch' (the
+    reference's draws: ``gumbel_samples`` on the CPU and ``F.dropout``, carried
+    to slot order by the op) or 'device' (seeded descriptors the op generates
+    on the device in slot order: :class:`mgcn.ops.DeviceGumbel` /
+    :class:`mgcn.ops.DeviceDropout` under :func:`mgcn.ops.draw_edge_seed`)."""
+    if edge_rng not in ('torch', 'device'):
+        raise ValueError(f"edge_rng must be 'torch' or 'device', got {edge_rng!r}")
+    return edge_rng
+
+
 def _combine_heads(y, nheads, channels_1head, combine, bias):
     """The head combine ('cat': none) and the bias after an attention op
     (graph_attention.py:102-117).  bf16 rows (a bf16 ``x``): both are
@@ -387,14 +399,19 @@ class NodeModelAttention(NodeModelBase):
     and with ``att_combine='cat'`` one head has out_channels / nheads channels
     (else out_channels each).  A bf16 ``x`` keeps bf16 rows through the op
     (fp32 master parameters or a module after ``.to(torch.bfloat16)``) and
-    gives a bf16 output; fp32 is the reference's arithmetic."""
+    gives a bf16 output; fp32 is the reference's arithmetic.
+    ``edge_rng='device'`` (:func:`_edge_rng`; default 'torch') has the
+    training dropout mask generated on the device, seeded from torch's CPU
+    generator."""
 
     def __init__(self, in_channels, out_channels, in_edgedim=None, nheads=1, att_act='none',
-                 att_dropout=0, att_combine='cat', att_dir='in', bias=False, **kwargs):
+                 att_dropout=0, att_combine='cat', att_dir='in', bias=False, edge_rng='torch',
+                 **kwargs):
         assert att_act in ['none', 'lrelu', 'relu']
         assert att_combine in ['cat', 'add', 'mean']
         assert att_dir in ['in', 'out']
         super().__init__(in_channels, out_channels, in_edgedim)
+        self.edge_rng = _edge_rng(edge_rng)
         self.nheads = nheads
         if att_combine == 'cat':
             self.out_channels_1head = out_channels // nheads
@@ -428,7 +445,9 @@ class NodeModelAttention(NodeModelBase):
         plan = plan_for(edge_index, x.size(0))
         hp = linear(x, self.weight)
         mask = None
-        if self.training and self.att_dropout.p > 0:
+        if self.training and self.att_dropout.p > 0 and self.edge_rng == 'device':
+            mask = DeviceDropout(self.att_dropout.p, *draw_edge_seed())
+        elif self.training and self.att_dropout.p > 0:
             # the reference's Dropout on alpha: alpha * mask with mask = dropout(ones)
             mask = nn.functional.dropout(
                 torch.ones(plan.nnz, self.nheads, dtype=torch.float32, device=hp.device),
@@ -472,15 +491,20 @@ class NodeModelHardAttention(NodeModelBase):
     :func:`mgcn.ops.linear`, everything after it on
     :func:`mgcn.ops.hard_attention_aggregate`, which also mirrors the
     reference's last-edge quirk for nodes without a neighbour.  Head widths
-    follow ``att_combine`` as in :class:`NodeModelAttention`."""
+    follow ``att_combine`` as in :class:`NodeModelAttention`.
+    ``edge_rng='device'`` (:func:`_edge_rng`; default 'torch') has the Gumbel
+    noise (training, and eval with ``sample``) and the training dropout mask
+    generated on the device, seeded from torch's CPU generator: no CPU draw,
+    no host-to-device copy, and ``gumbel_samples`` is not called."""
 
     def __init__(self, in_channels, out_channels, in_edgedim=None, nheads=1, att_act='none',
                  att_dropout=0, att_combine='cat', att_dir='in', bias=False, temperature=0.1,
-                 sample=False, **kwargs):
+                 sample=False, edge_rng='torch', **kwargs):
         assert att_act in ['none', 'lrelu', 'relu']
         assert att_combine in ['cat', 'add', 'mean']
         assert att_dir in ['in', 'out']
         super().__init__(in_channels, out_channels, in_edgedim)
+        self.edge_rng = _edge_rng(edge_rng)
         self.nheads = nheads
         if att_combine == 'cat':
             self.out_channels_1head = out_channels // nheads
@@ -518,10 +542,15 @@ class NodeModelHardAttention(NodeModelBase):
         plan = plan_for(edge_index, x.size(0))
         hp = linear(x, self.weight)
         noise = mask = None
-        if self.training or self.sample:
+        device_rng = self.edge_rng == 'device'
+        if (self.training or self.sample) and device_rng:
+            noise = DeviceGumbel(*draw_edge_seed())
+        elif self.training or self.sample:
             noise = gumbel_samples(torch.empty(plan.nnz, self.nheads, dtype=torch.float32,
                                                device=hp.device))
-        if self.training and self.att_dropout.p > 0:
+        if self.training and self.att_dropout.p > 0 and device_rng:
+            mask = DeviceDropout(self.att_dropout.p, *draw_edge_seed())
+        elif self.training and self.att_dropout.p > 0:
             mask = nn.functional.dropout(
                 torch.ones(plan.nnz, self.nheads, dtype=torch.float32, device=hp.device),
                 p=self.att_dropout.p, training=True)

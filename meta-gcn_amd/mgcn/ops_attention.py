@@ -26,6 +26,7 @@ from . import _lib as L
 from ._call import _contig_f32, launch
 from .graph import GraphPlan
 from .ops_gemm import gemm_tn
+from .ops_noise import DeviceDropout, DeviceGumbel, edge_noise
 
 BF16 = torch.bfloat16
 
@@ -240,7 +241,8 @@ def _check_args(who: str, Hp, att_weight, plan: GraphPlan, nheads: int, act: str
     tensors that must live on Hp's device.  Returns the rows [N, H C], the
     fp32 attention vector [H, 2C] and H."""
     _require_row_dtype(Hp, "Hp")
-    L.require_device(Hp, att_weight, plan.fwd.rowptr, *others)
+    L.require_device(Hp, att_weight, plan.fwd.rowptr,
+                     *(t for t in others if not isinstance(t, (DeviceGumbel, DeviceDropout))))
     if act not in L.ATT_ACT_CODES:
         raise ValueError(f"act must be one of none/lrelu/relu, got {act!r}")
     if att_dir not in ('in', 'out'):
@@ -261,9 +263,13 @@ def _check_args(who: str, Hp, att_weight, plan: GraphPlan, nheads: int, act: str
 
 
 def _slot_mask(edge_mask, plan: GraphPlan, H: int):
-    """``edge_mask`` [E, H] (COO order; None stays None) as fp32 in fwd slot order."""
+    """``edge_mask`` [E, H] (COO order; None stays None) as fp32 in fwd slot
+    order; a :class:`DeviceDropout` is generated in that order."""
     if edge_mask is None:
         return None
+    if isinstance(edge_mask, DeviceDropout):
+        return edge_noise(plan, H, L.NOISE_DROPOUT, seed=edge_mask.seed, offset=edge_mask.offset,
+                          p=edge_mask.p, order='fwd')
     if tuple(edge_mask.shape) != (plan.nnz, H):
         raise ValueError(f"edge_mask must be [{plan.nnz}, {H}] in COO order, got "
                          f"{tuple(edge_mask.shape)}")
@@ -281,7 +287,7 @@ def _alpha_coo(alpha, mask, plan: GraphPlan):
 
 def attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphPlan, nheads: int,
                         act: str = 'none', att_dir: str = 'in',
-                        edge_mask: torch.Tensor | None = None):
+                        edge_mask: torch.Tensor | DeviceDropout | None = None):
     """Multi-head soft attention over each node's neighbourhood
     (graph_attention.py:66-100 + the softmax of common.py:69-92), fused:
 
@@ -289,7 +295,9 @@ def attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphP
     [1, H, 2C] (or [H, 2C]) the attention vector, ``act`` in none / lrelu /
     relu, ``att_dir`` 'in' (softmax over the edges into a node) or 'out' (over
     the edges out of it).  ``edge_mask`` [E, H], in COO edge order, multiplies
-    the attention coefficients (the dropout mask with its 1 / (1 - p) scale).
+    the attention coefficients (the dropout mask with its 1 / (1 - p) scale);
+    a :class:`mgcn.ops.DeviceDropout` instead of a tensor has that mask made
+    by one ``mgcn_edge_noise`` launch, directly in the order the kernels read.
 
     Returns ``(Y, alpha_coo)``: Y [N, H * C] = sum over in-edges of alpha' *
     Hp[src], and alpha' = alpha * mask as [E, H] in COO order, detached.
@@ -407,8 +415,8 @@ class _HardAttentionEval(torch.autograd.Function):
 def hard_attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: GraphPlan,
                              nheads: int, act: str = 'none', att_dir: str = 'in',
                              temperature: float = 0.1, *, training: bool,
-                             noise: torch.Tensor | None = None,
-                             edge_mask: torch.Tensor | None = None):
+                             noise: torch.Tensor | DeviceGumbel | None = None,
+                             edge_mask: torch.Tensor | DeviceDropout | None = None):
     """Multi-head hard attention over each node's neighbourhood
     (graph_hard_attention.py:82-139), fused.  Arguments as for
     :func:`attention_aggregate`, plus:
@@ -425,6 +433,13 @@ def hard_attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: G
     Differentiable in Hp only; ``att_weight`` receives no gradient and
     ``edge_mask`` is not used (the reference drops out in training alone).
 
+    ``noise`` may be a :class:`mgcn.ops.DeviceGumbel` and ``edge_mask`` a
+    :class:`mgcn.ops.DeviceDropout` instead of tensors: each is then made by
+    one ``mgcn_edge_noise`` launch in the slot order its kernel reads (the
+    walked view for the noise, fwd for the mask), with the values
+    :func:`mgcn.ops.edge_noise` gives in COO order under the same seed and
+    offset, and no COO tensor or permutation in between.
+
     Returns ``(Y, alpha_coo)``: Y [N, H * C] and the coefficients that weighted
     the messages, [E, H] in COO order, detached.  ``Hp`` float32 or bfloat16 as
     for :func:`attention_aggregate`."""
@@ -435,7 +450,10 @@ def hard_attention_aggregate(Hp: torch.Tensor, att_weight: torch.Tensor, plan: G
         raise ValueError(f"temperature must be positive, got {temperature!r}")
     # the view whose rows are the softmax / argmax groups
     walked = plan.fwd if att_dir == 'in' or (training and plan.nnz == 0) else plan.bwd
-    if noise is not None:
+    if isinstance(noise, DeviceGumbel):
+        noise = edge_noise(plan, H, L.NOISE_GUMBEL, seed=noise.seed, offset=noise.offset,
+                           order='fwd' if walked is plan.fwd else 'bwd')
+    elif noise is not None:
         if tuple(noise.shape) != (plan.nnz, H):
             raise ValueError(f"noise must be [{plan.nnz}, {H}] in COO order, got "
                              f"{tuple(noise.shape)}")

@@ -31,8 +31,8 @@ from torch.nn import Parameter
 from torch.nn.utils.rnn import pad_sequence
 
 from .graph import adopt_derived, plan_for
-from .models import Linear, activation, glorot, zeros
-from .ops import hard_attention_aggregate, linear
+from .models import Linear, _edge_rng, activation, glorot, zeros
+from .ops import DeviceDropout, DeviceGumbel, draw_edge_seed, hard_attention_aggregate, linear
 from .pool import scatter_max_arg
 
 
@@ -137,11 +137,14 @@ class VotePoolLayer(nn.Module):
     with att_dir 'out' (every node chooses where to send its feature),
     aggregation at the targets, then pruning by :func:`get_edge_select` /
     :func:`prune`.  ``aggr``: 'add' is the kernel's sum, 'mean' that sum
-    divided by max(in-degree, 1); 'max' is not implemented."""
+    divided by max(in-degree, 1); 'max' is not implemented.
+    ``edge_rng='device'`` (default 'torch', this module's ``gumbel_samples``):
+    noise and dropout mask generated on the device, as for
+    :class:`mgcn.models.NodeModelHardAttention`."""
 
     def __init__(self, in_channels, out_channels, nheads=1, att_act='none', att_dropout=0,
                  att_combine='cat', att_dir='out', bias=False, aggr='add', temperature=0.1,
-                 sample=False, p_keep=None, relabel=False, **kwargs):
+                 sample=False, p_keep=None, relabel=False, edge_rng='torch', **kwargs):
         assert att_act in ['none', 'lrelu', 'relu']
         assert att_combine in ['cat', 'add', 'mean']
         assert att_dir == 'out'
@@ -151,6 +154,7 @@ class VotePoolLayer(nn.Module):
                 "(use 'add' or 'mean')")
         assert aggr in ['add', 'mean']
         super().__init__()
+        self.edge_rng = _edge_rng(edge_rng)
         self.in_channels = in_channels
         self.out_channels = out_channels
         self.aggr = aggr
@@ -187,10 +191,15 @@ class VotePoolLayer(nn.Module):
         plan = plan_for(edge_index, x.size(0))
         hp = linear(x, self.weight)
         noise = mask = None
-        if self.training or self.sample:
+        device_rng = self.edge_rng == 'device'
+        if (self.training or self.sample) and device_rng:
+            noise = DeviceGumbel(*draw_edge_seed())
+        elif self.training or self.sample:
             noise = gumbel_samples(torch.empty(plan.nnz, self.nheads, dtype=torch.float32,
                                                device=hp.device))
-        if self.training and self.att_dropout.p > 0:
+        if self.training and self.att_dropout.p > 0 and device_rng:
+            mask = DeviceDropout(self.att_dropout.p, *draw_edge_seed())
+        elif self.training and self.att_dropout.p > 0:
             mask = nn.functional.dropout(
                 torch.ones(plan.nnz, self.nheads, dtype=torch.float32, device=hp.device),
                 p=self.att_dropout.p, training=True)
