@@ -1615,6 +1615,52 @@ int mgcn_csr_derive(
 int mgcn_edge_noise(int kind, uint64_t seed, uint64_t offset, int64_t nnz, int32_t H,
                     const int32_t *eid, float p, float *out, void *stream);
 
+/*
+ * Neighbour sampling (sample.hip): the COO keep mask that caps every
+ * destination row at `fanout` neighbours drawn without replacement, for
+ * mgcn_edge_rank / mgcn_csr_derive to turn into a child plan.  A
+ * backward-compatible addition: MGCN_ABI_VERSION stays 22.
+ *
+ * The view is the fwd one (rows = destinations, col = sources, eid = COO ids).
+ *   key(e)      output word 0, all 32 bits, of the Philox4x32-10 call that
+ *               mgcn_edge_noise makes for head 0: key (seed & 0xffffffff,
+ *               seed >> 32), counter (e, 0, offset & 0xffffffff, offset >> 32);
+ *               key(e) >> 8 is UNIFORM's u of that edge times 2^24
+ *   candidates  keep_loops != 0: an edge with col == row is no candidate, it
+ *               is kept and does not count against the fan-out; keep_loops
+ *               == 0: loops are candidates like any other edge
+ *   selection   the candidates of a row ordered by (key(e), e) ascending, a
+ *               strict total order; the first min(fanout, #candidates) are
+ *               kept (fanout == 0: no candidate)
+ *   row_mask    [n_rows] bytes or NULL: a row with row_mask[row] == 0 keeps
+ *               nothing, loops included
+ * keep [nnz] is in COO order and every entry is written, 0 or 1.  It is a
+ * function of the arguments above alone -- integers only: not of the slot
+ * order, of the route a row takes, of the launch shape or of the device.
+ *
+ * order / n_heavy: the view's row schedule (mgcn_row_schedule).  Rows
+ * order[0, n_heavy) go one to a workgroup (a radix select of the fanout-th
+ * smallest (key << 32) | e, any row length); rows order[n_heavy, n_rows) must
+ * have at most 128 slots, the schedule's default threshold, and go to lane
+ * groups.  order NULL (n_heavy 0): natural row order, and the rows above 128
+ * slots are found by a walk over the row pointers: the same mask, slower.
+ *
+ * No workspace is needed (mgcn_sample_rows_workspace_bytes is 0 and workspace
+ * may be NULL), nothing is allocated, the launches go to `stream`.
+ * MGCN_EINVAL before any launch, keep untouched: n_rows < 0, nnz < 0, nnz >=
+ * 2^31, fanout < 0, n_heavy outside [0, n_rows], order NULL with n_heavy > 0,
+ * and with nnz > 0: keep, rowptr or eid NULL, col NULL with keep_loops.
+ * nnz == 0 or n_rows == 0 succeeds and launches nothing.  rowptr, eid and
+ * order are a plan's own (mgcn_csr_build) and are not validated; a store
+ * whose COO id is outside [0, nnz) is suppressed.
+ */
+size_t mgcn_sample_rows_workspace_bytes(int64_t n_rows, int64_t nnz);
+int mgcn_sample_rows(int64_t n_rows, int64_t nnz, const int64_t *rowptr, const int32_t *col,
+                     const int32_t *eid, const int32_t *order, int64_t n_heavy,
+                     const uint8_t *row_mask, int32_t fanout, int keep_loops, uint64_t seed,
+                     uint64_t offset, uint8_t *keep, void *workspace, size_t workspace_bytes,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

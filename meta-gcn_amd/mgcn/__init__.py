@@ -20,7 +20,8 @@ from .graph import (GraphPlan, adopt_plan, build_plan, clear_cache, drop_edges, 
                     set_derived_plans)
 from .ops import (DeviceDropout, DeviceGumbel, aggregate, attention_aggregate, draw_edge_seed,
                   edge_noise, gate_aggregate, hard_attention_aggregate, multi_aggregate,
-                  scatter_, segment_mean)
+                  sample_keep, sample_layers, sample_neighbors, scatter_, segment_mean,
+                  set_sample_heavy_rows)
 
 __version__ = "0.1.0"
 
@@ -28,4 +29,5 @@ __all__ = ["MgcnError", "check_device", "load", "set_option", "GraphPlan", "buil
            "clear_cache", "aggregate", "attention_aggregate", "gate_aggregate",
            "multi_aggregate", "hard_attention_aggregate", "scatter_", "segment_mean", "_lib",
            "adopt_plan", "drop_edges", "set_derived_plans", "edge_noise", "DeviceGumbel",
-           "DeviceDropout", "draw_edge_seed"]
+           "DeviceDropout", "draw_edge_seed", "sample_keep", "sample_neighbors", "sample_layers",
+           "set_sample_heavy_rows"]

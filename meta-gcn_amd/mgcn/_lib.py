@@ -255,6 +255,9 @@ SIGNATURES = {
     "mgcn_csr_derive": (_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp,
                                _vp, _vp, _vp, _sz, _vp]),
     "mgcn_edge_noise": (_int, [_int, _u64, _u64, _i64, _i32, _vp, _f32, _vp, _vp]),
+    "mgcn_sample_rows_workspace_bytes": (_sz, [_i64, _i64]),
+    "mgcn_sample_rows": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _int, _u64, _u64,
+                                _vp, _vp, _sz, _vp]),
 }
 
 class PackedTableC(ctypes.Structure):

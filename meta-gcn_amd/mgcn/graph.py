@@ -259,6 +259,16 @@ class GraphPlan:
         eid_new, total = _edge_rank(self, keep, None)
         return _derive(self, eid_new, int(total), self.num_nodes, None, None)
 
+    def sample_neighbors(self, fanout: int, *, seed: int | None = None, offset: int = 0,
+                         keep_loops: bool = True, rows: torch.Tensor | None = None):
+        """``(child_plan, keep)``: every destination row capped at ``fanout``
+        in-neighbours drawn without replacement on the device under
+        ``(seed, offset)`` (``seed=None``: one ``draw_edge_seed()`` pair), the
+        child derived by :meth:`select_edges` -- :func:`mgcn.ops_sample.sample_neighbors`."""
+        from .ops_sample import sample_neighbors
+        return sample_neighbors(self, fanout, seed=seed, offset=offset, keep_loops=keep_loops,
+                                rows=rows)
+
     def induced(self, nodes, relabel: bool = False, validate: bool = True) -> "GraphPlan":
         """The plan of the subgraph induced by ``nodes``, a bool mask
         [num_nodes] or a list of node ids in any order.
