@@ -1661,6 +1661,69 @@ int mgcn_sample_rows(int64_t n_rows, int64_t nnz, const int64_t *rowptr, const i
                      uint64_t offset, uint8_t *keep, void *workspace, size_t workspace_bytes,
                      void *stream);
 
+/*
+ * Mini-batch blocks (block.hip): one hop of a sampled multi-hop frontier,
+ * built in time proportional to the frontier -- no pass reads or writes an
+ * array sized by the parent's nnz (node-sized ones: yes).  Backward-compatible
+ * additions: MGCN_ABI_VERSION stays 22.
+ *
+ * dst [n_dst] int32 is the hop's destination list D (distinct parent node
+ * ids, any order); the parent is given by its fwd view (rows = destinations,
+ * col = sources, eid = COO ids), n_nodes rows and nnz slots.  The block's
+ * edges are the slots mgcn_sample_rows keeps under (fanout, keep_loops, seed,
+ * offset) with D as its row mask -- the same definition, byte for byte --,
+ * ordered by (position of the row in D, slot order inside the row); a block
+ * edge's id is its position.  Its nodes: D in list order (local ids 0 ..
+ * n_dst - 1), then the other sources, ascending (n_dst .. n_src - 1).
+ *
+ * Three calls per hop on one stream with the same workspace
+ * (mgcn_block_workspace_bytes(n_nodes, n_dst) bytes: it carries state from
+ * one call to the next), the caller reading two device words in between to
+ * size the outputs:
+ *
+ * mgcn_block_count   node_map [n_nodes]: D[i] -> i, every other node -1;
+ *   rowptr_out [n_dst + 1]: the block's fwd row pointers; meta [5] int64 on
+ *   the device: meta[0] = nnz_out (the block's edges), meta[1] = n_heavy (rows
+ *   of D above 128 slots), meta[2] != 0: an id of D outside [0, n_nodes),
+ *   meta[3] != 0: an id listed twice (the block of such a list is not
+ *   defined; every store stays inside the arrays), meta[4] = 0.
+ * mgcn_block_fill    nnz_out and n_heavy as read from meta.  src_out /
+ *   eid_out [nnz_out] int32: the parent id of every block edge's source and
+ *   its parent COO id; dst_out [nnz_out] int64: its destination's local id.
+ *   meta[4] = the number of sources outside D.  Rows of D above 128 slots go
+ *   one to a workgroup wherever they stand in the list; neither that nor the
+ *   lane-group width changes a byte.
+ * mgcn_block_relabel n_src = n_dst + meta[4].  node_map gains the new
+ *   sources' local ids; src_ids [n_src] int64: the parent id of every local
+ *   id; col_out [nnz_out] int32 and coo_src [nnz_out] int64: every block
+ *   edge's source in local ids.  (coo_src, dst_out) is the block's COO list:
+ *   its fwd view is (rowptr_out extended by its last entry to n_src + 1 rows,
+ *   col_out, eid = 0 .. nnz_out - 1), its bwd view mgcn_csr_build of the list.
+ *
+ * Nothing is allocated and no call waits for the device.  MGCN_EINVAL before
+ * any launch: a negative size, nnz, n_nodes or n_dst >= 2^31, fanout < 0,
+ * nnz_out outside [0, nnz], n_heavy outside [0, n_dst], n_src outside [n_dst,
+ * n_nodes], a NULL array that the sizes say is read or written;
+ * MGCN_EWORKSPACE for a short workspace.  n_dst == 0, fanout == 0 and nnz ==
+ * 0 succeed and describe empty blocks.  The parent's arrays are a plan's own
+ * and are not validated.
+ */
+size_t mgcn_block_workspace_bytes(int64_t n_nodes, int64_t n_dst);
+int mgcn_block_count(int64_t n_nodes, int64_t nnz, const int64_t *rowptr, const int32_t *col,
+                     const int32_t *dst, int64_t n_dst, int32_t fanout, int keep_loops,
+                     int32_t *node_map, int64_t *rowptr_out, int64_t *meta, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int mgcn_block_fill(int64_t n_nodes, int64_t nnz, const int64_t *rowptr, const int32_t *col,
+                    const int32_t *eid, const int32_t *dst, int64_t n_dst, int32_t fanout,
+                    int keep_loops, uint64_t seed, uint64_t offset, const int64_t *rowptr_out,
+                    int64_t nnz_out, int64_t n_heavy, const int32_t *node_map, int32_t *src_out,
+                    int32_t *eid_out, int64_t *dst_out, int64_t *meta, void *workspace,
+                    size_t workspace_bytes, void *stream);
+int mgcn_block_relabel(int64_t n_nodes, const int32_t *dst, int64_t n_dst, int64_t n_src,
+                       int64_t nnz_out, const int32_t *src_out, int32_t *node_map,
+                       int64_t *src_ids, int32_t *col_out, int64_t *coo_src, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,8 @@
 //    keep_loops, row_mask, seed, offset): integers only, so neither the slot
 //    order, the route of a row nor the launch shape can change a byte.
 //
-// Two kernels, every row in exactly one of them:
+// Two kernels, every row in exactly one of them (the selection they run is
+// sample_select.h's light_row / heavy_pick, which block.hip runs too):
 //   sample_light_kernel<G>  rows of at most kLight = 128 slots, one lane group
 //       of G lanes per row (G from the mean degree).  A row whose candidates
 //       fit the fan-out stores its ones without a Philox call.  Otherwise the
@@ -26,57 +27,22 @@
 // + nnz (4 + 4 + 1) (rowptr, col, eid, the keep byte).
 
 #include "mgcn_internal.h"
-#include "philox.h"
+#include "sample_select.h"
 
 namespace mgcn {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kLight = 128;              // slots of a light row (the row schedule's heavy threshold)
-constexpr int kTileStride = kLight + 1;  // u64 entries: the groups' tiles start two banks apart
-constexpr int kCap = 7168;               // slots of a heavy row whose keys stay in LDS (56 KB)
-constexpr unsigned kMaxGrid = 8192;      // grid-stride beyond (cdna_hip_programming.md G11)
-constexpr uint64_t kNotCand = ~uint64_t(0);  // no composite: e < 2^31
-static_assert(kBlock == 256, "one thread per bin of the radix histogram");
+using namespace sampling;  // the selection itself: sample_select.h
 
-struct SampleArgs {
-  int64_t n_rows, nnz;
-  const int64_t *rowptr;
-  const int32_t *col, *eid, *order;
+struct SampleArgs : SelectArgs {
+  const int32_t *order;
   int64_t n_heavy;
   const uint8_t *row_mask;
-  uint32_t fanout;
-  int keep_loops;
-  uint32_t key0, key1, off0, off1;
   uint8_t *keep;
 };
 
-// word 0 of mgcn_edge_noise's call for head 0 of COO edge e
-__device__ __forceinline__ uint32_t edge_key(const SampleArgs &a, uint32_t e) {
-  uint32_t c[4] = {e, 0u, a.off0, a.off1};
-  philox4x32_10(c, a.key0, a.key1);
-  return c[0];
-}
-
 __device__ __forceinline__ void put(const SampleArgs &a, int32_t e, bool v) {
   if ((uint64_t)(uint32_t)e < (uint64_t)a.nnz) a.keep[e] = v ? 1 : 0;
-}
-
-// What a row that needs no selection stores in slot k: nothing of a masked
-// row, everything where the candidates fit, else (fanout == 0) the loops.
-__device__ __forceinline__ bool fill_value(const SampleArgs &a, bool masked, bool all, int64_t r,
-                                           int64_t k) {
-  if (masked) return false;
-  if (all) return true;
-  return a.keep_loops && a.col[k] == (int32_t)r;
-}
-
-// A group's tile is written and read by lanes of one wave alone, whose LDS
-// operations complete in order: no workgroup barrier, only the compiler's.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 template <int G>
@@ -101,165 +67,22 @@ __global__ __launch_bounds__(kBlock) void sample_light_kernel(SampleArgs a) {
       }
     }
     const bool masked = d > 0 && a.row_mask != nullptr && a.row_mask[r] == 0;
-    // the lane's first slot (the only one of a row of at most G) rides in
-    // registers: its eid and col loads go out together
-    const bool has0 = lg < d;
-    int32_t e0 = 0;
-    bool cand0 = false;
-    if (has0) {
-      e0 = a.eid[s0 + lg];
-      cand0 = !a.keep_loops || a.col[s0 + lg] != (int32_t)r;
-    }
-    int cand = d;
-    if (a.keep_loops) {
-      int c = cand0 ? 1 : 0;
-      for (int j = lg + G; j < d; j += G) c += a.col[s0 + j] != (int32_t)r ? 1 : 0;
-#pragma unroll
-      for (int off = G / 2; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
-      cand = c;
-    }
-    const bool select = !masked && a.fanout > 0 && (uint32_t)cand > a.fanout;
-    uint64_t mine0 = kNotCand;
-    if (select) {
-      if (has0) {
-        if (cand0) mine0 = ((uint64_t)edge_key(a, (uint32_t)e0) << 32) | (uint32_t)e0;
-        tile[lg] = mine0;
-      }
-      for (int j = lg + G; j < d; j += G) {
-        const int32_t e = a.eid[s0 + j];
-        const bool is_cand = !a.keep_loops || a.col[s0 + j] != (int32_t)r;
-        tile[j] = is_cand ? ((uint64_t)edge_key(a, (uint32_t)e) << 32) | (uint32_t)e : kNotCand;
-      }
-    }
-    wave_sync();
-    if (select) {
-      auto rank_put = [&](uint64_t mine, int32_t e) {
-        bool kept = true;
-        if (mine != kNotCand) {
-          uint32_t rank = 0;
-          for (int t = 0; t < d; ++t) rank += tile[t] < mine ? 1u : 0u;
-          kept = rank < a.fanout;
-        }
-        put(a, e, kept);
-      };
-      if (has0) rank_put(mine0, e0);
-      for (int j = lg + G; j < d; j += G) rank_put(tile[j], a.eid[s0 + j]);
-    } else if (d > 0) {
-      const bool all = (uint32_t)cand <= a.fanout;
-      if (has0) put(a, e0, masked ? false : all ? true : (a.keep_loops && !cand0));
-      for (int j = lg + G; j < d; j += G)
-        put(a, a.eid[s0 + j], fill_value(a, masked, all, r, s0 + j));
-    }
-    wave_sync();  // the tiles are rewritten next round
+    light_row<G>(a, r, s0, d, masked, tile, lg,
+                 [&](int, int32_t e, bool kept) { put(a, e, kept); });
   }
-}
-
-struct HeavyLds {
-  uint32_t key[kCap];
-  uint32_t e[kCap];  // bit 31: not a candidate (a kept loop)
-  uint32_t hist[256];
-  uint32_t wave[kBlock / 64];
-  uint32_t bin, excl;
-  uint8_t flag[kBlock];
-};
-
-// inclusive prefix sum of v over the workgroup's threads; *total: the sum
-__device__ inline uint32_t block_scan_incl(uint32_t v, uint32_t *s_wave, uint32_t *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t t = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += t;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kBlock / 64; ++w) {
-    const uint32_t t = s_wave[w];
-    base += w < wave ? t : 0u;
-    tot += t;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc;
 }
 
 // One row by the whole workgroup; every branch that returns is uniform.
 __device__ void heavy_row(const SampleArgs &a, int64_t r, HeavyLds &s) {
-  const int tid = threadIdx.x;
   const int64_t s0 = a.rowptr[r];
   const int64_t d = a.rowptr[r + 1] - s0;
   if (d <= 0) return;
   const bool masked = a.row_mask != nullptr && a.row_mask[r] == 0;
-  uint32_t cand = (uint32_t)d;
-  if (!masked && a.keep_loops) {
-    uint32_t c = 0;
-    for (int64_t j = tid; j < d; j += kBlock) c += a.col[s0 + j] != (int32_t)r ? 1u : 0u;
-    block_scan_incl(c, s.wave, &cand);
-  }
-  if (masked || cand <= a.fanout || a.fanout == 0) {
-    const bool all = cand <= a.fanout;
-    for (int64_t j = tid; j < d; j += kBlock)
-      put(a, a.eid[s0 + j], fill_value(a, masked, all, r, s0 + j));
-    return;
-  }
-  const bool cached = d <= kCap;
-  if (cached) {
-    for (int64_t j = tid; j < d; j += kBlock) {
-      const int32_t e = a.eid[s0 + j];
-      const bool is_cand = !a.keep_loops || a.col[s0 + j] != (int32_t)r;
-      s.key[j] = is_cand ? edge_key(a, (uint32_t)e) : 0u;
-      s.e[j] = (uint32_t)e | (is_cand ? 0u : 0x80000000u);
-    }
-  }
-  // slot j: its COO id, its composite, whether it is a candidate
-  auto load = [&](int64_t j, int32_t &e, uint64_t &comp) -> bool {
-    if (cached) {
-      const uint32_t w = s.e[j];
-      e = (int32_t)(w & 0x7fffffffu);
-      comp = ((uint64_t)s.key[j] << 32) | (w & 0x7fffffffu);
-      return (w >> 31) == 0;
-    }
-    e = a.eid[s0 + j];
-    if (a.keep_loops && a.col[s0 + j] == (int32_t)r) {
-      comp = 0;
-      return false;
-    }
-    comp = ((uint64_t)edge_key(a, (uint32_t)e) << 32) | (uint32_t)e;
-    return true;
-  };
-  // the k-th smallest composite (k = fanout < cand), a byte per pass from the top
-  uint64_t prefix = 0;
-  uint32_t k = a.fanout;
-  for (int pass = 7; pass >= 0; --pass) {
-    const int shift = pass * 8;
-    s.hist[tid] = 0;
-    __syncthreads();  // (first pass: the cached keys are in place too)
-    for (int64_t j = tid; j < d; j += kBlock) {
-      int32_t e;
-      uint64_t comp;
-      if (load(j, e, comp) && (pass == 7 || (comp >> (shift + 8)) == prefix))
-        atomicAdd(&s.hist[(uint32_t)(comp >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    const uint32_t v = s.hist[tid];
-    uint32_t tot;
-    const uint32_t inc = block_scan_incl(v, s.wave, &tot);
-    if (inc - v < k && k <= inc) {  // one bin: 1 <= k <= tot
-      s.bin = (uint32_t)tid;
-      s.excl = inc - v;
-    }
-    __syncthreads();
-    prefix = (prefix << 8) | s.bin;
-    k -= s.excl;
-  }
-  for (int64_t j = tid; j < d; j += kBlock) {
+  const HeavyPick p = heavy_pick(a, r, s0, d, masked, s);
+  for (int64_t j = threadIdx.x; j < d; j += kBlock) {
     int32_t e;
-    uint64_t comp;
-    const bool is_cand = load(j, e, comp);
-    put(a, e, !is_cand || comp <= prefix);
+    const bool kept = heavy_kept(a, p, s, r, s0, j, e);
+    put(a, e, kept);
   }
 }
 
@@ -335,9 +158,8 @@ extern "C" int mgcn_sample_rows(int64_t n_rows, int64_t nnz, const int64_t *rowp
   }
   if (nnz == 0 || n_rows == 0) return MGCN_OK;
   hipStream_t s = as_stream(stream);
-  const SampleArgs a{n_rows, nnz, rowptr, col, eid, order, order != nullptr ? n_heavy : 0,
-                     row_mask, (uint32_t)fanout, keep_loops ? 1 : 0, (uint32_t)seed,
-                     (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), keep};
+  const SampleArgs a{select_args(n_rows, nnz, rowptr, col, eid, fanout, keep_loops, seed, offset),
+                     order, order != nullptr ? n_heavy : 0, row_mask, keep};
   // heavy rows first: the longest work starts earliest
   if (order != nullptr) {
     if (n_heavy > 0) {

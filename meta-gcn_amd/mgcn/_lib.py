@@ -258,6 +258,13 @@ SIGNATURES = {
     "mgcn_sample_rows_workspace_bytes": (_sz, [_i64, _i64]),
     "mgcn_sample_rows": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _int, _u64, _u64,
                                 _vp, _vp, _sz, _vp]),
+    "mgcn_block_workspace_bytes": (_sz, [_i64, _i64]),
+    "mgcn_block_count": (_int, [_i64, _i64, _vp, _vp, _vp, _i64, _i32, _int, _vp, _vp, _vp, _vp,
+                                _sz, _vp]),
+    "mgcn_block_fill": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _int, _u64, _u64, _vp,
+                               _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mgcn_block_relabel": (_int, [_i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                  _vp]),
 }
 
 class PackedTableC(ctypes.Structure):

@@ -269,6 +269,15 @@ class GraphPlan:
         return sample_neighbors(self, fanout, seed=seed, offset=offset, keep_loops=keep_loops,
                                 rows=rows)
 
+    def sample_blocks(self, seeds, fanouts, *, seed: int | None = None, offset: int = 0,
+                      keep_loops: bool = True, validate: bool = True) -> list:
+        """The mini-batch blocks of ``seeds``, one per entry of ``fanouts``,
+        built on the device in time proportional to the frontier --
+        :func:`mgcn.ops_block.sample_blocks`."""
+        from .ops_block import sample_blocks
+        return sample_blocks(self, seeds, fanouts, seed=seed, offset=offset,
+                             keep_loops=keep_loops, validate=validate)
+
     def induced(self, nodes, relabel: bool = False, validate: bool = True) -> "GraphPlan":
         """The plan of the subgraph induced by ``nodes``, a bool mask
         [num_nodes] or a list of node ids in any order.
