@@ -1724,6 +1724,51 @@ int mgcn_block_relabel(int64_t n_nodes, const int32_t *dst, int64_t n_dst, int64
                        int64_t *src_ids, int32_t *col_out, int64_t *coo_src, void *workspace,
                        size_t workspace_bytes, void *stream);
 
+/*
+ * Aggregation on a mini-batch block (block_conv.hip): rectangular launches
+ * over the block's own views, PyG's self-loop rules folded in, so no edge
+ * list is edited and no plan is built.  Backward-compatible additions:
+ * MGCN_ABI_VERSION stays 22.
+ *
+ * The block has n_dst destinations (local ids 0 .. n_dst - 1) among n_src
+ * nodes, n_dst <= n_src.  `loops` says what a slot whose two ends are the same
+ * node (an in-row self loop) does:
+ *   MGCN_LOOPS_KEEP    it counts like any slot;
+ *   MGCN_LOOPS_DROP    it adds nothing and its source row never reaches the
+ *                      sum (PyG's remove_self_loops);
+ *   MGCN_LOOPS_APPEND  dropped likewise, then one term X[i] * w_loop closes
+ *                      row i (PyG 1.3's add_remaining_self_loops: w_loop = 1
+ *                      without weights, else the weight of the row's last loop
+ *                      slot, or `fill` where the row has none).
+ *
+ * mgcn_block_spmm_fwd  Y [n_dst, F] from X [n_src, F]: row i folded in slot
+ *   order (= COO order) with separately rounded products and sums, as
+ *   mgcn_spmm_fwd folds it; rowptr [n_dst + 1] is the head of the block's fwd
+ *   row pointers, w (nullable) [nnz] in slot order.  MEAN divides by max(c, 1),
+ *   c = the slots that counted (+ 1 under APPEND), written to cnt [n_dst]
+ *   (nullable) as a float.  A row without counted slots gives 0 (KEEP / DROP)
+ *   or X[i] * w_loop (APPEND).
+ * mgcn_block_spmm_bwd  dX [n_src, F] from dY [n_dst, F] over the block's bwd
+ *   view (rows = sources): per slot k the term g * w[eid_t[k]], g = dY[col_k]
+ *   (MEAN: dY[col_k] / cnt[col_k], the forward's cnt), loop slots as above;
+ *   under APPEND rows s < n_dst end with g(dY[s]) * w_loop.
+ *
+ * Any F >= 1 and leading dimensions >= F; rows of any length (a long row is
+ * walked by its lane group).  No atomics, no workspace, nothing allocated.
+ * MGCN_EINVAL before any HIP call: a negative size, n_dst > n_src, n_src >=
+ * 2^31, F < 1, a leading dimension < F, reduce other than SUM / MEAN, a bad
+ * `loops`, a NULL array that is read or written (col / col_t / eid_t may be
+ * NULL for a block without edges), MEAN in the adjoint without cnt.
+ */
+enum { MGCN_LOOPS_KEEP = 0, MGCN_LOOPS_DROP = 1, MGCN_LOOPS_APPEND = 2 };
+int mgcn_block_spmm_fwd(int64_t n_dst, int64_t n_src, int32_t F, const int64_t *rowptr,
+                        const int32_t *col, const float *w, float fill, int loops, const float *X,
+                        int64_t ldx, float *Y, int64_t ldy, int reduce, float *cnt, void *stream);
+int mgcn_block_spmm_bwd(int64_t n_src, int64_t n_dst, int32_t F, const int64_t *rowptr_t,
+                        const int32_t *col_t, const int32_t *eid_t, const float *w, float fill,
+                        int loops, const float *dY, int64_t lddy, float *dX, int64_t lddx,
+                        int reduce, const float *cnt, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

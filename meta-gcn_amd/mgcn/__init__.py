@@ -19,10 +19,10 @@ from ._lib import MgcnError, check_device, load, set_option
 from .graph import (GraphPlan, adopt_plan, build_plan, clear_cache, drop_edges, plan_for,
                     set_derived_plans)
 from .ops import (Block, DeviceDropout, DeviceGumbel, aggregate, attention_aggregate,
-                  block_batches, draw_edge_seed, edge_noise, gate_aggregate,
-                  hard_attention_aggregate, multi_aggregate, sample_blocks, sample_keep,
+                  block_aggregate, block_batches, block_convs, draw_edge_seed, edge_noise,
+                  gate_aggregate, hard_attention_aggregate, multi_aggregate, sample_blocks, sample_keep,
                   sample_layers, sample_neighbors, scatter_, segment_mean,
-                  set_sample_heavy_rows)
+                  set_block_convs, set_sample_heavy_rows)
 
 __version__ = "0.1.0"
 
@@ -31,4 +31,5 @@ __all__ = ["MgcnError", "check_device", "load", "set_option", "GraphPlan", "buil
            "multi_aggregate", "hard_attention_aggregate", "scatter_", "segment_mean", "_lib",
            "adopt_plan", "drop_edges", "set_derived_plans", "edge_noise", "DeviceGumbel",
            "DeviceDropout", "draw_edge_seed", "sample_keep", "sample_neighbors", "sample_layers",
-           "set_sample_heavy_rows", "Block", "sample_blocks", "block_batches"]
+           "set_sample_heavy_rows", "Block", "sample_blocks", "block_batches", "block_aggregate",
+           "set_block_convs", "block_convs"]

@@ -265,6 +265,10 @@ SIGNATURES = {
                                _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mgcn_block_relabel": (_int, [_i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                   _vp]),
+    "mgcn_block_spmm_fwd": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _f32, _int, _vp, _i64, _vp,
+                                   _i64, _int, _vp, _vp]),
+    "mgcn_block_spmm_bwd": (_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _int, _vp, _i64,
+                                   _vp, _i64, _int, _vp, _vp]),
 }
 
 class PackedTableC(ctypes.Structure):

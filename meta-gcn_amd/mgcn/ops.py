@@ -43,6 +43,9 @@ from .ops_noise import (NOISE_KINDS, DeviceDropout, DeviceGumbel, draw_edge_seed
 from .ops_sample import (sample_heavy_rows, sample_keep, sample_layers,  # noqa: F401
                          sample_neighbors, set_sample_heavy_rows)
 from .ops_block import Block, block_batches, sample_blocks  # noqa: F401
+from .ops_block_conv import (LOOPS_CODES, _BlockAggregate, block_aggregate,  # noqa: F401
+                             block_conv_supported, block_convs, block_spmm_bwd, block_spmm_fwd,
+                             set_block_convs)
 from .ops_gate import (_GateAggregate, _GateAggregateBf16, gate_aggregate,  # noqa: F401
                        gate_heavy_rows, set_gate_heavy_rows)
 from .ops_multi import (_MultiAggregate, multi_aggregate, multi_kernel_fusable,  # noqa: F401

@@ -15,7 +15,9 @@ layer's input rows::
 
     h = x[blocks[0].src_ids]
     for l, conv in enumerate(convs):
-        h = conv(h, blocks[l].edge_index)[:blocks[l].n_dst]
+        h = conv(h, blocks[l])  # or conv(h, blocks[l].edge_index)[:blocks[l].n_dst]
+
+(:mod:`mgcn.ops_block_conv` has what a conv does with a block).
 """
 from __future__ import annotations
 

@@ -20,6 +20,18 @@ below are PyG 1.3.x's, chosen and recorded in DESIGN.md:
 * SAGEConv  add_remaining_self_loops; mean_j (w_j x_j) then @ W, + bias,
             optional L2 normalise.
 * GraphConv (sum|mean|max)_j (w_j * (x_j @ W)) + Linear(x); no self loops.
+
+Mini-batch blocks: every conv's forward takes a :class:`mgcn.Block` where it
+takes ``edge_index``; ``x`` then has ``block.n_src`` rows and the result
+``block.n_dst``.  Where :func:`mgcn.ops.block_conv_supported` holds, SAGEConv,
+GINConv and GraphConv (add / mean) aggregate the destinations alone through
+:func:`mgcn.block_aggregate` -- the self-loop rule folded into the launch, no
+edge list edited, no plan built -- and run the dense product on ``n_dst`` rows.
+Otherwise (heavy rows, bf16 rows, a differentiable edge_weight, GraphConv's
+max, GCNConv, ``mgcn.set_block_convs(False)``) the call is
+``conv(x, block.edge_index, ...)[:block.n_dst]``.  The two routes agree bit for
+bit on the aggregate; at fused shapes (128 -> 128) the fallback's one-launch
+(A x) W associates its sums differently from aggregate-then-GEMM.
 """
 from __future__ import annotations
 
@@ -35,6 +47,8 @@ from torch.nn import Parameter
 from .graph import cache_key, plan_for
 from .models import Linear, glorot, zeros
 from .ops import aggregate_plan, gcn_layer, linear, scatter_
+from .ops_block import Block
+from .ops_block_conv import block_aggregate, block_conv_supported
 
 
 def uniform(size, tensor):
@@ -158,6 +172,10 @@ class GCNConv(nn.Module):
         zeros(self.bias)
 
     def forward(self, x, edge_index, edge_weight=None, relu=False):
+        if isinstance(edge_index, Block):
+            # the symmetric norm over a block's own degrees is the fallback's
+            block = edge_index
+            return self.forward(x, block.edge_index, edge_weight, relu)[:block.n_dst]
         N = x.size(0)
         fill = 2 if self.improved else 1
         if edge_weight is None:
@@ -194,6 +212,12 @@ class GINConv(nn.Module):
 
     def forward(self, x, edge_index):
         x = x.unsqueeze(-1) if x.dim() == 1 else x
+        if isinstance(edge_index, Block):
+            block = edge_index
+            if not block_conv_supported(block, x, None):
+                return self.forward(x, block.edge_index)[:block.n_dst]
+            agg = block_aggregate(x, block, 'add', 'drop')
+            return self.nn((1 + self.eps) * x[:block.n_dst] + agg)
         N = x.size(0)
         ei = _without_loops(edge_index, N)
         plan = plan_for(ei, N)
@@ -229,6 +253,20 @@ class SAGEConv(nn.Module):
 
     def forward(self, x, edge_index, edge_weight=None, size=None):
         x = x.unsqueeze(-1) if x.dim() == 1 else x
+        if isinstance(edge_index, Block):
+            block = edge_index
+            if not block_conv_supported(block, x, edge_weight):
+                return self.forward(x, block.edge_index, edge_weight, size)[:block.n_dst]
+            # the mean over the row's edges and the appended loop, then @ W + b
+            out = block_aggregate(x, block, 'mean', 'append', edge_weight, 1.0)
+            if self.concat:
+                out = torch.cat([x[:block.n_dst], out], dim=-1)
+            out = linear(out, self.weight)
+            if self.bias is not None:
+                out = out + self.bias
+            if self.normalize:
+                out = F.normalize(out, p=2, dim=-1)
+            return out
         N = x.size(0)
         ei, ew = _with_loops(edge_index, edge_weight, N, 1)
         plan = plan_for(ei, N)
@@ -272,6 +310,13 @@ class GraphConv(nn.Module):
 
     def forward(self, x, edge_index, edge_weight=None, size=None):
         x = x.unsqueeze(-1) if x.dim() == 1 else x
+        if isinstance(edge_index, Block):
+            block = edge_index
+            if self.aggr == 'max' or not block_conv_supported(block, x, edge_weight):
+                return self.forward(x, block.edge_index, edge_weight, size)[:block.n_dst]
+            # sum / mean commute with W: aggregate first, the GEMM on n_dst rows
+            agg = block_aggregate(x, block, self.aggr, 'keep', edge_weight)
+            return linear(agg, self.weight) + self.lin(x[:block.n_dst])
         plan = plan_for(edge_index, x.size(0))
         norm = plan.norm(None, edge_weight=edge_weight)
         if self.aggr == 'max':
